@@ -2,7 +2,7 @@
 """Headline benchmark: DBNet (ResNet18-FPN-DBHead) training images/s at 640x640, bs 16 per GPU,
 fp32, synthetic data (BASELINE.json `metric`, configs[1]; the path of SURVEY.md §8).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A step is one iteration of the reference's loop (train.py:160-172): forward, DBLoss,
 backward, [one RCCL all-reduce of the flat gradients when N > 1], Adam — all HIP kernels of
@@ -20,6 +20,7 @@ Extra objects on the JSON line:
   roofline_hbm  the DB-head group (head tail forward / backward, DBLoss forward / backward) against the HBM peak: on the
                 fused kernels' own bytes and on SURVEY section 8d's unfused-algorithmic 84 B/px
   cpu_baseline  the CPU oracle (oracle/dbnet_oracle.py, plain PyTorch fp32) timed on this host
+  dump_outputs  with --dump-outputs DIR: the arrays of the LAST timed step written to DIR (see dump_outputs below)
   parity        BEFORE the timed region: one step of the benchmarked configuration on the inputs of tests/golden/cfg2_16x640.npz
                 (the reference's own train step at 16x3x640x640) — distances of the three maps and the five losses from the
                 reference's numbers; the run exits non-zero above the north_star tolerance
@@ -306,6 +307,34 @@ def dry_run(args):
     return 0 if ok else 4
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, preds, losses):
+    """--dump-outputs DIR: what trainer.step returned in the last timed step, as DIR/<name>.npy in float32 — `losses.npy` (the five
+    DBLoss values) and `preds.npy` (the probability / threshold / binary maps, flattened).  When the maps exceed the 64 MB budget
+    (16x3x640x640 fp32 is 78.6 MB), `preds.npy` holds a fixed sample of them: the flat indices drawn without replacement by
+    numpy's default_rng(DUMP_SAMPLE_SEED), in ascending order — the same indices for the same --batch / --size.  The inputs and the
+    initial weights are seeded, so two builds run with the same arguments can be compared array for array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    losses = losses.detach().float().cpu().numpy().reshape(-1)
+    flat = preds.detach().float().cpu().numpy().reshape(-1)
+    room = (DUMP_BUDGET_BYTES - losses.nbytes - 4096) // 4  # (4 KB for the .npy headers)
+    sampled = flat.size > room
+    if sampled:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.size, size=room, replace=False))
+        flat = flat[idx]
+    arrays = {'preds': np.ascontiguousarray(flat, dtype=np.float32), 'losses': np.ascontiguousarray(losses, dtype=np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {'dir': os.path.abspath(out_dir), 'step': 'last timed step', 'dtype': 'float32',
+            'arrays': {name: list(a.shape) for name, a in arrays.items()}, 'preds_shape': list(preds.shape),
+            'preds_sampled': ('%d of %d elements, flat indices from numpy default_rng(%d).choice(without replacement), ascending'
+                              % (room, preds.numel(), DUMP_SAMPLE_SEED)) if sampled else None}
+
+
 def launched_by():
     if os.environ.get('DBN_BENCH_SELF_LAUNCHED') == '1':
         return 'bench.py --gpus N (self-launched torch.distributed.run child)'
@@ -361,7 +390,14 @@ def main():
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'], help='process-group backend (nccl = RCCL; gloo only with --dry)')
     ap.add_argument('--dry', action='store_true', help='launch / rendezvous / exchange plumbing only, no GPU work (CPU test of --gpus N)')
     ap.add_argument('--no-parity', action='store_true', help='skip the cfg2_16x640 parity gate that runs before the timed region')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned (predicted maps, the five losses) as DIR/<name>.npy '
+                         '(float32, at most 64 MB: a fixed, seeded sample of the maps when they are larger)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.dry:
+        ap.error('--dump-outputs needs the real step: --dry computes nothing')
     if args.backend != 'nccl' and not args.dry and os.environ.get('DBN_DIST_ONE_DEVICE', '0') != '1':
         raise SystemExit('--backend gloo is for --dry runs (the step itself has no CPU path) and for the one-GPU rehearsal of an '
                          'N-rank run (DBN_DIST_ONE_DEVICE=1: every rank on device 0, device tensors through gloo; tests/test_dist2_gpu.py)')
@@ -458,6 +494,9 @@ def main():
     final_loss = float(losses[4])
     if not (final_loss == final_loss):
         raise SystemExit('non-finite loss')
+    # the last timed step's outputs, copied before any later step (other exchange form, instrumented steps, alternative modes) reuses
+    # their buffers
+    dumped = dump_outputs(args.dump_outputs, preds, losses) if args.dump_outputs and rank == 0 else None
 
     # ---- N > 1 diagnostics: exposed part of the exchange, the other exchange form, replica divergence ------------------
     def exposed_ms(events):
@@ -698,6 +737,8 @@ def main():
             'final_total_loss': round(final_loss, 5),
             'parity': parity,
         }
+        if dumped is not None:
+            line['dump_outputs'] = dumped
         if not args.no_cpu_baseline and world == 1:  # reported at N=1 only
             line['cpu_baseline'] = cpu_baseline()
         print(json.dumps(line), flush=True)

@@ -194,3 +194,31 @@ def test_bench_refuses_more_gpus_than_visible_and_wrong_world_size():
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--dry', '--backend', 'gloo'], env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and 'WORLD_SIZE=1' in (r.stderr + r.stdout)
+
+
+def test_bench_dump_outputs_fits_the_budget_and_samples_the_same_elements(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files of at most 64 MB in all; maps larger than that (16x3x640x640 fp32) are a sample
+    whose indices depend only on the shape, so two runs (two builds) compare element for element; small maps are written whole."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(0)
+    preds, losses = torch.rand(16, 3, 640, 640, generator=g), torch.rand(5, generator=g)
+    info = bench.dump_outputs(str(tmp_path / 'a'), preds, losses)
+    bench.dump_outputs(str(tmp_path / 'b'), preds.clone(), losses.clone())
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['losses.npy', 'preds.npy'] and info['preds_sampled']
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 64 * 10**6
+    for f in files:
+        a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    p = np.load(tmp_path / 'a' / 'preds.npy')
+    assert np.isin(p[:1000], preds.numpy().ravel()).all()
+    np.testing.assert_array_equal(np.load(tmp_path / 'a' / 'losses.npy'), losses.numpy())
+    small = torch.rand(2, 3, 64, 64, generator=g)
+    assert bench.dump_outputs(str(tmp_path / 'c'), small, losses)['preds_sampled'] is None
+    np.testing.assert_array_equal(np.load(tmp_path / 'c' / 'preds.npy'), small.numpy().ravel())
+
+
+def test_bench_refuses_zero_steps():
+    r = _run_bench('--steps', '0', '--dry', '--backend', 'gloo')
+    assert r.returncode != 0 and '--steps' in r.stderr
