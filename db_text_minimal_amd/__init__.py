@@ -4,3 +4,4 @@ from .losses import DBLoss  # noqa: F401
 from .models import DBTextModel  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
 from .train import DBTrainer  # noqa: F401
+from .gt_maps import gt_collate, make_gt_maps, normalize_images, offset_polygon  # noqa: F401

@@ -33,6 +33,9 @@ SIGNATURES = {
     'dbn_permute_weight': 'ppiiiifp',
     'dbn_binarize_u8': 'piiiifpp',
     'dbn_box_scores': 'piipiipp',
+    'dbn_gt_maps': 'ppppp' + 'iiiii' + 'ff' + 'pp',
+    'dbn_normalize_u8': 'piiifffpp',
+    'dbn_poly_offset': 'pippip',
     'dbn_pyramid_conv_ws_floats': 'iiii',
     'dbn_pyramid_conv_f32': 'p' * 10 + 'i' * 7 + 'pp' + 'ff' + 'ppppppp' + 'p',
     'dbn_conv_bn_f32': 'pppp' + 'i' * 15 + 'pp' + 'ff' + 'ppppppp' + 'p',

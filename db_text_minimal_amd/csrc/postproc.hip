@@ -3,10 +3,9 @@
 //   binarize_u8      postprocess.py:51-52    pred[:, 0] > thresh, as a uint8 bitmap (1 B/px over PCIe instead of 4)
 //   box_scores       postprocess.py:186-198  box_score_fast for K boxes/polygons at once: mean of the probability map
 //                                            over the cv2.fillPoly mask of each box (one workgroup per box)
-// The fillPoly mask is evaluated per pixel in closed form: a pixel is set if it lies on the 8-connected Bresenham
-// line of an edge (LineIterator, left-to-right) or inside the even-odd scanline fill in 16.16 fixed point
-// (OpenCV drawing.cpp: fillPoly -> CollectPolyEdges + FillEdgeCollection, Line -> LineIterator; XY_SHIFT = 16).
+// The fillPoly mask is evaluated per pixel in closed form (fillpoly.h, shared with gtmaps.hip).
 #include "common.h"
+#include "fillpoly.h"
 
 namespace {
 
@@ -22,26 +21,6 @@ __global__ void binarize_u8_kernel(const float* __restrict__ pred, long plane_st
         b.x = v[0] > thresh; b.y = v[1] > thresh; b.z = v[2] > thresh; b.w = v[3] > thresh;
         reinterpret_cast<uchar4*>(out)[i] = b;
     }
-}
-
-__device__ __forceinline__ long long trunc_div(long long a, long long b) { return a / b; }  // C++: toward zero, like OpenCV
-
-// pixel (px,py) on the 8-connected line from (xa,ya) to (xb,yb)?
-__device__ __forceinline__ bool on_line(int px, int py, int xa, int ya, int xb, int yb) {
-    int dx = xb - xa, dy = yb - ya, x1 = xa, y1 = ya;
-    if (dx < 0) { x1 = xb; y1 = yb; dx = -dx; dy = -dy; }
-    const int sy = dy < 0 ? -1 : 1;
-    dy = dy < 0 ? -dy : dy;
-    if (dy > dx) {  // steep: one pixel per row
-        const int i = (py - y1) * sy;
-        if (i < 0 || i > dy) return false;
-        const int m = (2 * dx * i + dy - 1) / (2 * dy);
-        return px == x1 + m;
-    }
-    const int i = px - x1;
-    if (i < 0 || i > dx) return false;
-    const int m = dx == 0 ? 0 : (2 * dy * i + dx - 1) / (2 * dx);
-    return py == y1 + sy * m;
 }
 
 __global__ __launch_bounds__(256) void box_score_kernel(const float* __restrict__ bitmap, int H, int W,
@@ -72,21 +51,7 @@ __global__ __launch_bounds__(256) void box_score_kernel(const float* __restrict_
     double sum = 0.0, cnt = 0.0;
     for (int idx = threadIdx.x; idx < bw * bh; idx += blockDim.x) {
         const int py = idx / bw, px = idx - py * bw;
-        bool in = false;
-        int A = 0, B = 0;
-        for (int i = 0; i < P; ++i) {
-            const int j = i == 0 ? P - 1 : i - 1;
-            int xa = vx[j], ya = vy[j], xb = vx[i], yb = vy[i];
-            in = in || on_line(px, py, xa, ya, xb, yb);
-            if (ya == yb) continue;
-            if (ya > yb) { int t = xa; xa = xb; xb = t; t = ya; ya = yb; yb = t; }
-            if (py < ya || py >= yb) continue;
-            const long long dxf = trunc_div((long long)(xb - xa) << 16, (long long)(yb - ya));
-            const long long xe = ((long long)xa << 16) + (long long)(py - ya) * dxf;
-            A += ((xe + 65535) >> 16) <= px;
-            B += (xe >> 16) < px;
-        }
-        in = in || A > B || (B & 1);
+        const bool in = dbn_fillpoly_hit(px, py, vx, vy, P);
         if (in) {
             sum += (double)bitmap[(long)(ymin + py) * W + xmin + px];
             cnt += 1.0;

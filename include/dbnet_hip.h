@@ -395,6 +395,28 @@ int dbn_binarize_u8(const float* pred, int N, int channels, int H, int W, float 
  * vertices are padded by repeating the last vertex. */
 int dbn_box_scores(const float* bitmap, int H, int W, const float* boxes, int K, int P, float* scores, void* stream);
 
+/* ---- ground truth of data_loaders.py:87-172 on the device (csrc/gtmaps.hip, db_text_minimal_amd/gt_maps.py) ---- */
+/* The four maps of train.py GT_KEYS for N images of S x S pixels: out[4][N][S][S] fp32 (prob_map, supervision_mask,
+ * thresh_map, text_area_map).  P polygons, image by image: polygons img_off[n] .. img_off[n+1]-1 belong to image n.
+ * meta[P][20] int32 per polygon: 0 first vertex in verts (fp64 (x, y) pairs), 1 vertex count (<= 64), 2 ignored flag,
+ * 3/4 first point / count in ixy (int32 (x, y) pairs) of the shrunk polygon (the truncated source polygon if ignored),
+ * 5/6 first point / count in ixy of the padded polygon, 7-10 the box x0 x1 y0 y1 of pixels the polygon may touch
+ * (clamped to the image; empty if x1 < x0), 11-14 the padded polygon's bbox xmin xmax ymin ymax, 15-18 the bbox of
+ * the shrunk (or truncated) polygon, 19 unused.  dist[P] = D of each polygon (fp64).  max_verts / max_off_pts: bounds
+ * on the vertex counts (meta 1) and ixy counts (meta 4, 6) of every polygon, refused above 64 / 1024.  Precondition: no
+ * count exceeds them (the Python layer passes the batch's maxima and refuses larger polygons before the call); the kernel
+ * draws nothing for a polygon that breaks it, it never clips one.  thresh_map = canvas * scale + tmin in fp32. */
+int dbn_gt_maps(const double* verts, const double* dist, const int* meta, const int* img_off, const int* ixy, int N, int P, int S,
+                int max_verts, int max_off_pts, float scale, float tmin, float* out, void* stream);
+/* uint8 in[N][H][W][3] -> fp32 out[N][3][H][W] = (float)in - m_c (data_loaders.py:161-167; the reference's means in
+ * image channel order) */
+int dbn_normalize_u8(const unsigned char* in, int N, int H, int W, float m0, float m1, float m2, float* out, void* stream);
+/* host: Clipper 6 ClipperOffset (JT_ROUND, ET_CLOSEDPOLYGON, ArcTolerance 0.25) of the closed path xy[n][2] by *delta
+ * (fp64, by pointer), coordinates cast to integers toward zero as pyclipper converts them.  Writes the piece of largest
+ * area to out_xy[*out_n][2] (*out_n = 0: the offset vanished); returns 1 with *out_n = the needed count if it exceeds
+ * cap.  PARITY UNPINNED against pyclipper. */
+int dbn_poly_offset(const double* xy, int n, const double* delta, int* out_xy, int cap, int* out_n);
+
 
 /* =====================================================================================================================
  * Activation storage types (BASELINE configs[2]-[4]).  Every entry point above that moves activation tensors has a `_t`
