@@ -10,6 +10,7 @@
 // (-1, H) x (-1, W) is zero; each corner contributes only if its index is inside the image.
 // Offsets: channel 2k = dy, 2k+1 = dx of tap k = r*S + s, stored [M][off_stride] (off_stride >= 2*R*S).
 #include "common.h"
+#include <float.h>
 #include <stdlib.h>
 
 namespace {
@@ -105,7 +106,9 @@ __global__ __launch_bounds__(256) void absmax_kernel(const void* __restrict__ x,
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         const f32x4 v = dbn_ld4<AT>(x, i);
         const float a = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
-        bad |= !(fabsf(v[0]) <= 3.0e38f) | !(fabsf(v[1]) <= 3.0e38f) | !(fabsf(v[2]) <= 3.0e38f) | !(fabsf(v[3]) <= 3.0e38f);  // (fmaxf drops a NaN)
+        // finite <=> |v| <= FLT_MAX (false for a NaN, which fmaxf would drop); a bound below FLT_MAX reported the largest finite values,
+        // bf16's among them, as non-finite
+        bad |= !(fabsf(v[0]) <= FLT_MAX) | !(fabsf(v[1]) <= FLT_MAX) | !(fabsf(v[2]) <= FLT_MAX) | !(fabsf(v[3]) <= FLT_MAX);
         m = fmaxf(a, m);
     }
 #pragma unroll
@@ -300,7 +303,7 @@ __global__ __launch_bounds__(256) void deform_bbox_kernel(const void* __restrict
             int n, ho, wo;
             const Sample sp = sample_of<AT>(d, offset, m, k, n, ho, wo);
             const float oy = fabsf(dbn_ld1<AT>(offset, (long)m * d.off_stride + 2 * k)), ox = fabsf(dbn_ld1<AT>(offset, (long)m * d.off_stride + 2 * k + 1));
-            bad |= !(oy <= 3.0e38f) | !(ox <= 3.0e38f);  // (fmaxf drops a NaN)
+            bad |= !(oy <= FLT_MAX) | !(ox <= FLT_MAX);  // (fmaxf drops a NaN; the same finiteness test as absmax_kernel)
             om = fmaxf(om, fmaxf(oy, ox));
             if (sp.inside) {
                 ymin = min(ymin, sp.y0);

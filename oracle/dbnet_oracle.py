@@ -233,20 +233,19 @@ def _bn(sd, prefix, x, training, update_stats):
     return F.batch_norm(x, None, None, w, b, True, BN_MOMENTUM, BN_EPS)
 
 
-def deform_conv2d(x, offset, weight, stride=1, pad=1):
-    """torchvision.ops.deform_conv2d (v0.6.0, deformable_groups = 1, dilation 1, no bias) restated from DCNv1:
-    out[n,co,ho,wo] = sum_{ci,k} w[co,ci,k] * bilinear(x[n,ci], ho*stride - pad + r_k + dy_k, wo*stride - pad + s_k + dx_k),
-    offset channel 2k = dy_k, 2k+1 = dx_k over the R*S taps k = r*S + s; samples outside (-1, H) x (-1, W) are zero and
-    each of the four corner reads is zero when its index is out of range (bilinear_interpolate of deform_conv2d_kernel).
-    Built from gathers, so autograd yields the gradients w.r.t. x, offset and weight.
-    PARITY UNPINNED: torchvision is not installed here and absent from /root/reference; pinned only by the
-    zero-offset identity with F.conv2d and by finite differences (tests/test_oracle_golden.py)."""
+def deform_sample(x, offset, R, S, stride=1, pad=1):
+    """The sampling of torchvision.ops.deform_conv2d (v0.6.0, deformable_groups = 1, dilation 1) restated from DCNv1:
+    col[n,c,k,ho,wo] = bilinear(x[n,c], ho*stride - pad + r_k + dy_k, wo*stride - pad + s_k + dx_k), offset channel
+    2k = dy_k, 2k+1 = dx_k over the R*S taps k = r*S + s -> [N, C, R*S, Ho, Wo].  The rule is bilinear_interpolate of
+    deform_conv2d_kernel: a sample outside (-1, H) x (-1, W) is zero; otherwise y0 = floor(y), x0 = floor(x), the corner
+    weights are (1-ly)(1-lx), (1-ly)lx, ly(1-lx), ly lx with ly = y - y0, lx = x - x0, and each of the four corner reads
+    is zero when its index is out of range.  A non-finite offset makes its sample's C values NaN (its weights are NaN) and
+    touches nothing else.  Built from gathers, so autograd yields the gradients w.r.t. x and offset."""
     N, C, H, W = x.shape
-    Co, _, R, S = weight.shape
     Ho, Wo = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
     assert offset.shape == (N, 2 * R * S, Ho, Wo), offset.shape
-    ho = torch.arange(Ho, dtype=x.dtype).view(1, Ho, 1) * stride - pad
-    wo = torch.arange(Wo, dtype=x.dtype).view(1, 1, Wo) * stride - pad
+    ho = torch.arange(Ho, dtype=x.dtype, device=x.device).view(1, Ho, 1) * stride - pad
+    wo = torch.arange(Wo, dtype=x.dtype, device=x.device).view(1, 1, Wo) * stride - pad
     xf = x.reshape(N, C, H * W)
     cols = []
     for k in range(R * S):
@@ -260,11 +259,23 @@ def deform_conv2d(x, offset, weight, stride=1, pad=1):
         for (yy, xc, wgt) in ((y0, x0, (1 - ly) * (1 - lx)), (y0, x0 + 1, (1 - ly) * lx), (y0 + 1, x0, ly * (1 - lx)),
                               (y0 + 1, x0 + 1, ly * lx)):
             ok = inside & (yy >= 0) & (yy <= H - 1) & (xc >= 0) & (xc <= W - 1)
+            # (a non-finite position reads nothing; its index only has to be valid: the corner's weight is NaN * 0 = NaN)
+            yy, xc = torch.where(torch.isfinite(yy), yy, 0), torch.where(torch.isfinite(xc), xc, 0)
             idx = (yy.clamp(0, H - 1) * W + xc.clamp(0, W - 1)).long().view(N, 1, Ho * Wo).expand(N, C, Ho * Wo)
             g = torch.gather(xf, 2, idx).view(N, C, Ho, Wo)
             val = val + g * (wgt * ok.to(x.dtype)).unsqueeze(1)
         cols.append(val)
-    col = torch.stack(cols, 2)  # [N, C, RS, Ho, Wo]
+    return torch.stack(cols, 2)  # [N, C, RS, Ho, Wo]
+
+
+def deform_conv2d(x, offset, weight, stride=1, pad=1):
+    """torchvision.ops.deform_conv2d (v0.6.0, deformable_groups = 1, dilation 1, no bias) restated from DCNv1:
+    out[n,co,ho,wo] = sum_{ci,k} w[co,ci,k] * deform_sample(x, offset)[n,ci,k,ho,wo].
+    PARITY UNPINNED: torchvision is not installed and the reference does not vendor it; pinned only by the
+    zero-offset identity with F.conv2d, by finite differences (tests/test_oracle_golden.py) and by the analytic pins of
+    deform_sample's boundary rule (tests/test_oracle_deform_cpu.py)."""
+    Co, C, R, S = weight.shape
+    col = deform_sample(x, offset, R, S, stride, pad)
     return torch.einsum('ock,nckhw->nohw', weight.reshape(Co, C, R * S), col)
 
 

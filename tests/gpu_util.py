@@ -80,6 +80,15 @@ def reduce_ws():
     return torch.empty(L().dbn_reduce_ws_floats(512), device=DEV)
 
 
+def col_sum_depth(M, C):
+    """Longest serial fp32 chain of dbn_col_sum_t (csrc/pointwise.hip channel_reduce): nb = min(ceil(M / 64), 768) blocks of
+    ceil(M / nb) rows; in a chunk of Cc = min(C, 1024) channels, 256 / (Cc / 4) row lanes share a block's rows and are then added in LDS."""
+    nb = min(max(-(-M // 64), 1), 768)
+    rows = -(-M // nb)
+    nrl = max(256 // (min(C, 1024) // 4), 1)
+    return -(-rows // nrl) + nrl
+
+
 def rnd(*shape, seed=0, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     return torch.randn(*shape, generator=g) * scale
