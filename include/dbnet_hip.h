@@ -417,6 +417,31 @@ int dbn_normalize_u8(const unsigned char* in, int N, int H, int W, float m0, flo
  * cap.  PARITY UNPINNED against pyclipper. */
 int dbn_poly_offset(const double* xy, int n, const double* delta, int* out_xy, int cap, int* out_n);
 
+/* ---- text boxes from probability maps: boxes_from_bitmap of postprocess.py:105-141 (csrc/detect.hip,
+ *      db_text_minimal_amd/postprocess.py detect_boxes).  PARITY UNPINNED against cv2 / pyclipper. ---- */
+/* One record per candidate (72 bytes):
+ *   struct dbn_detect_rec { int root, hull_n, ex, ey; long long dmin, dmax, cmin, cmax, sum_hi, sum_lo, count; };
+ * root: raster index y*W+x of the component's first pixel (-1: empty slot); hull_n: vertices of the convex hull of its
+ * pixel centres (-1: hull buffer overflow); the min-area rectangle R1 of that hull has a side along the integer edge
+ * vector (ex, ey) and spans dot((ex, ey), v) over [dmin, dmax], cross((ex, ey), v) over [cmin, cmax]; the sum of pred
+ * over the filled component is sum_hi * 2^-24 + sum_lo * 2^-56 over `count` pixels (fixed point; pred clamped to
+ * [-127, 127], bits below 2^-56 dropped). */
+/* bytes of workspace dbn_detect needs */
+long dbn_detect_ws_bytes(int N, int H, int W, int max_candidates);
+/* Device stage for pred[N][channels][H][W] (fp32, channel 0 used), bitmap = pred > thresh, H, W <= 16384:
+ * labels[N][H][W] int32 = root (raster index of the first pixel) of each pixel's component, foreground 8-connected,
+ * background 4-connected; counts[n] = number of foreground components; recs[N][max_candidates] dbn_detect_rec, slot k
+ * of image n = the foreground component with the k-th LARGEST root (k < min(counts[n], max_candidates)).  No float
+ * atomics: bitwise reproducible.  ws: dbn_detect_ws_bytes(...) bytes, any contents. */
+int dbn_detect(const float* pred, int N, int channels, int H, int W, float thresh, int max_candidates, void* ws, int* labels, void* recs,
+               int* counts, void* stream);
+/* host: postprocess.py:118-140 on the records of dbn_detect (host memory).  params = {box_thresh, unclip_ratio} (fp64),
+ * dest_hw[N][2] = (height, width) to scale to.  Writes, for k < min(counts[n], max_candidates), boxes[n][k][4][2] int16
+ * and scores[n][k] fp32 (zero for a skipped candidate); info (NULL or [N][max_candidates][10] fp32): R1's four corners,
+ * min side of R1, score of every candidate. */
+int dbn_detect_host(const void* recs, const int* counts, int N, int max_candidates, int H, int W, const double* params, const int* dest_hw,
+                    short* boxes, float* scores, float* info);
+
 
 /* =====================================================================================================================
  * Activation storage types (BASELINE configs[2]-[4]).  Every entry point above that moves activation tensors has a `_t`
