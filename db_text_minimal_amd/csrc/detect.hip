@@ -24,6 +24,12 @@
 // Host stage (dbn_detect_host): the per-box geometry of postprocess.py:118-140 on the records: R1 corners, score,
 // get_mini_boxes order, unclip (shapely area / length + the Clipper restatement of gtmaps.hip), R2, scaling to
 // dest size.  PARITY UNPINNED against cv2 / pyclipper: see DESIGN.md "Text boxes on the device".
+//
+// Polygons (dbn_detect_poly, dbn_detect_poly_host): polygons_from_bitmap (postprocess.py:54-103) on the same candidates.
+// The device traces every kept candidate's outer border at once: cracks (pixel, side) with a successor from a 2 x 2 block,
+// Wyllie pointer jumping to each border's head, weights that mark CHAIN_APPROX_SIMPLE vertices, and a scatter of the
+// packed int16 vertices.  The host runs approxPolyDP, the fp64 score, the unclip with its path count, the min-area
+// rectangle check and the fp64 scaling.  See DESIGN.md section 17.
 #include <limits.h>
 #include <math.h>
 
@@ -33,6 +39,7 @@
 #include "common.h"
 
 extern "C" int dbn_poly_offset(const double* xy, int n, const double* delta, int* out_xy, int cap, int* out_n);  // gtmaps.hip
+extern "C" int dbn_poly_offset_paths(const double* xy, int n, const double* delta, int* out_xy, int cap, int* out_n, int* out_paths);
 
 namespace {
 
@@ -430,6 +437,264 @@ __global__ __launch_bounds__(256) void hull_kernel(const int* __restrict__ label
     }
 }
 
+// ---- outer borders of the kept candidates (dbn_detect_poly) -------------------------------------------------------
+// A crack is (pixel p of candidate C, side s) whose 4-neighbour across s is background or outside the image.  Sides
+// L, B, R, T (s = 0..3) are walked with C on the left on screen (y down): L down, B right, R up, T left.  Cracks facing
+// a hole of C (a background component X with parent(X) = C, see tree_kernel) are not enumerated, nor are the cracks of
+// components past max_candidates: every enumerated crack lies on the outer-border cycle of a kept candidate, and every
+// such cycle holds exactly one head, the L crack of C's first pixel.
+__constant__ int PC_DX[4] = {0, 1, 0, -1}, PC_DY[4] = {1, 0, -1, 0};  // motion along L, B, R, T
+__constant__ int PC_NX[4] = {-1, 0, 1, 0}, PC_NY[4] = {0, 1, 0, -1};  // toward the background across L, B, R, T
+constexpr int PC_MAX_ROUNDS = 32;                                     // > log2 of the cracks of a 16384^2 image
+
+__device__ __forceinline__ bool pc_fg(const unsigned char* bm, int H, int W, int x, int y) {
+    return x >= 0 && y >= 0 && x < W && y < H && bm[(long)y * W + x];
+}
+
+// bit s set: (p, s) is an enumerated crack.  bm, lab, edge, slot: one image's planes.
+__device__ __forceinline__ int pc_mask(const unsigned char* bm, const int* lab, const int* edge, const int* slot, int H, int W, int x, int y) {
+    const long p = (long)y * W + x;
+    if (!bm[p]) return 0;
+    const int c = lab[p];
+    if (slot[c] < 0) return 0;
+    int m = 0;
+    for (int s = 0; s < 4; ++s) {
+        const int nx = x + PC_NX[s], ny = y + PC_NY[s];
+        if (nx < 0 || ny < 0 || nx >= W || ny >= H) { m |= 1 << s; continue; }
+        const long q = (long)ny * W + nx;
+        if (bm[q]) continue;
+        const int b = lab[q];
+        if (!edge[b] && lab[b - 1] == c) continue;  // a hole of C (b is not in column 0: it does not touch the edge)
+        m |= 1 << s;
+    }
+    return m;
+}
+
+// exclusive prefix of v over the 256 threads of the block; *total = the block's sum
+__device__ __forceinline__ int block_scan_256(int v, int* red, int* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += u;
+    }
+    __syncthreads();
+    if (lane == 63) red[w] = inc;
+    __syncthreads();
+    int before = 0;
+    for (int k = 0; k < w; ++k) before += red[k];
+    *total = red[0] + red[1] + red[2] + red[3];
+    return before + inc - v;
+}
+
+__global__ __launch_bounds__(256) void crack_count_kernel(const unsigned char* __restrict__ bitmap, const int* __restrict__ labels,
+                                                          const int* __restrict__ edge, const int* __restrict__ slot, int H, int W,
+                                                          int* __restrict__ rowcnt) {
+    __shared__ int red[4];
+    const int n = blockIdx.y, y = blockIdx.x;
+    const long hw = (long)H * W, o = n * hw;
+    int cnt = 0;
+    for (int x = threadIdx.x; x < W; x += 256) cnt += __popc(pc_mask(bitmap + o, labels + o, edge + o, slot + o, H, W, x, y));
+    cnt = block_sum_256(cnt, red);
+    if (threadIdx.x == 0) rowcnt[(long)n * H + y] = cnt;
+}
+
+// exclusive prefix over all rows of the batch (crack ids are global); hdr[0] = total cracks; clears the round flags
+__global__ __launch_bounds__(1024) void crack_scan_kernel(const int* __restrict__ rowcnt, long rows, int* __restrict__ rowbase, int* __restrict__ hdr) {
+    __shared__ int part[1024];
+    const int t = threadIdx.x;
+    const long ch = (rows + 1023) / 1024, lo = min(t * ch, rows), hi = min(lo + ch, rows);
+    int s = 0;
+    for (long r = lo; r < hi; ++r) s += rowcnt[r];
+    part[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        int acc = 0;
+        for (int k = 0; k < 1024; ++k) { const int v = part[k]; part[k] = acc; acc += v; }
+        hdr[0] = acc;
+    }
+    if (t < PC_MAX_ROUNDS) hdr[1 + t] = 0;
+    __syncthreads();
+    int acc = part[t];
+    for (long r = lo; r < hi; ++r) { rowbase[r] = acc; acc += rowcnt[r]; }
+}
+
+// per pixel: its crack mask and the id of its first crack (row base + prefix in the row, left to right)
+__global__ __launch_bounds__(256) void crack_emit_kernel(const unsigned char* __restrict__ bitmap, const int* __restrict__ labels,
+                                                         const int* __restrict__ edge, const int* __restrict__ slot, int H, int W,
+                                                         const int* __restrict__ rowbase, unsigned char* __restrict__ mask, int* __restrict__ pxbase) {
+    __shared__ int red[4];
+    const int n = blockIdx.y, y = blockIdx.x;
+    const long hw = (long)H * W, o = n * hw, row = o + (long)y * W;
+    int base = rowbase[(long)n * H + y];
+    for (int x0 = 0; x0 < W; x0 += 256) {
+        const int x = x0 + (int)threadIdx.x;
+        const int m = x < W ? pc_mask(bitmap + o, labels + o, edge + o, slot + o, H, W, x, y) : 0;
+        int tot;
+        const int pre = block_scan_256(__popc(m), red, &tot);
+        if (x < W) { mask[row + x] = (unsigned char)m; pxbase[row + x] = base + pre; }
+        base += tot;
+    }
+}
+
+__device__ __forceinline__ int pc_id(const unsigned char* mask, const int* pxbase, long p, int s) {
+    return pxbase[p] + __popc(mask[p] & ((1 << s) - 1));
+}
+
+// per crack: successor (the 8-connected turning rule), key p * 4 + s, candidate n * M + slot, head flag; the successor
+// learns its predecessor's pixel
+__global__ __launch_bounds__(256) void crack_link_kernel(const unsigned char* __restrict__ bitmap, const int* __restrict__ labels,
+                                                         const int* __restrict__ slot, int H, int W, int max_cand,
+                                                         const unsigned char* __restrict__ mask, const int* __restrict__ pxbase,
+                                                         int* __restrict__ succ, int* __restrict__ ckey, int* __restrict__ ccand,
+                                                         int* __restrict__ prevpix, unsigned char* __restrict__ wflag) {
+    const int n = blockIdx.y, y = blockIdx.x;
+    const long hw = (long)H * W, o = n * hw;
+    const unsigned char* bm = bitmap + o;
+    for (int x = threadIdx.x; x < W; x += 256) {
+        const long p = (long)y * W + x;
+        const int m = mask[o + p];
+        if (!m) continue;
+        const int c = labels[o + p];
+        const int cand = (int)((long)n * max_cand + slot[o + c]);
+        for (int s = 0; s < 4; ++s) {
+            if (!((m >> s) & 1)) continue;
+            const int id = pc_id(mask, pxbase, o + p, s);
+            const int ax = x + PC_DX[s], ay = y + PC_DY[s], gx = ax + PC_NX[s], gy = ay + PC_NY[s];
+            int qx = x, qy = y, qs = (s + 1) & 3;
+            if (pc_fg(bm, H, W, gx, gy)) { qx = gx; qy = gy; qs = (s + 3) & 3; }
+            else if (pc_fg(bm, H, W, ax, ay)) { qx = ax; qy = ay; qs = s; }
+            const long q = (long)qy * W + qx;
+            int nx = id;  // (cannot happen: the successor is an enumerated crack of the same cycle)
+            if ((mask[o + q] >> qs) & 1) {
+                nx = pc_id(mask, pxbase, o + q, qs);
+                prevpix[nx] = (int)p;
+            }
+            succ[id] = nx;
+            ckey[id] = (int)(p * 4 + s);
+            ccand[id] = cand;
+            wflag[id] = (s == 0 && c == (int)p) ? 2 : 0;  // bit 1: the head of the cycle
+        }
+    }
+}
+
+// weight = 1 where a compressed vertex starts: the first crack of a pixel visit whose arrival and departure steps
+// differ.  Initialises the ranking: head -> itself with weight 0 (the terminal), any other crack -> its successor.
+__global__ void crack_weight_kernel(const int* __restrict__ hdr, int W, const int* __restrict__ succ, const int* __restrict__ ckey,
+                                    const int* __restrict__ prevpix, unsigned char* __restrict__ wflag, int* __restrict__ nA, int* __restrict__ dA) {
+    const long total = hdr[0];
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int p = ckey[i] >> 2, pp = prevpix[i];
+        int kept = 0;
+        if (pp != p) {  // a visit starts here: leave the pixel (at most 4 cracks of one pixel in a row)
+            int j = (int)i, q = p;
+            for (int k = 0; k < 4; ++k) {
+                j = succ[j];
+                q = ckey[j] >> 2;
+                if (q != p) break;
+            }
+            const int px = p % W, py = p / W;
+            const int adx = px - pp % W, ady = py - pp / W, ddx = q % W - px, ddy = q / W - py;
+            kept = (adx != ddx || ady != ddy) ? 1 : 0;
+        }
+        const int head = wflag[i] & 2;
+        wflag[i] = (unsigned char)(head | kept);
+        nA[i] = head ? (int)i : succ[i];
+        dA[i] = head ? 0 : kept;
+    }
+}
+
+// one round of Wyllie's pointer jumping: d += d[next], next = next[next].  flags[r] = something changed; a round after
+// one that changed nothing returns at once.
+__global__ void crack_jump_kernel(const int* __restrict__ hdr, int r, const int* __restrict__ sn, const int* __restrict__ sd,
+                                  int* __restrict__ dn, int* __restrict__ dd, int* __restrict__ flags) {
+    if (r > 0 && flags[r - 1] == 0) return;
+    const long total = hdr[0];
+    bool changed = false;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int nx = sn[i];
+        const int nn = sn[nx];
+        dd[i] = sd[i] + sd[nx];
+        dn[i] = nn;
+        changed |= nn != nx;
+    }
+    if (__ballot(changed) && (threadIdx.x & 63) == 0) atomicOr(flags + r, 1);
+}
+
+// rounds run: round 0 always, round r when round r - 1 changed something
+__device__ __forceinline__ int pc_rounds(const int* flags, int R) {
+    int e = 1;
+    while (e < R && flags[e - 1]) ++e;
+    return e;
+}
+
+// per candidate slot: compressed vertices K = weight from the head's successor to the head (1 for a single pixel, whose
+// only visit has no start), offsets (exclusive prefix over the batch); a single pixel writes its vertex here
+__global__ __launch_bounds__(1024) void cand_verts_kernel(const Rec* __restrict__ recs, long slots, int W, long hw, int max_cand,
+                                                          const int* __restrict__ hdr, int R, const unsigned char* __restrict__ mask,
+                                                          const int* __restrict__ pxbase, const int* __restrict__ succ,
+                                                          const int* __restrict__ dA, const int* __restrict__ dB, int* __restrict__ nv,
+                                                          int* __restrict__ voff, int* __restrict__ info, short* __restrict__ verts) {
+    __shared__ int part[1024];
+    const int t = threadIdx.x;
+    const int E = pc_rounds(hdr + 1, R);
+    const int* d = (E - 1) % 2 == 0 ? dB : dA;
+    const long ch = (slots + 1023) / 1024, lo = min(t * ch, slots), hi = min(lo + ch, slots);
+    int s = 0;
+    for (long k = lo; k < hi; ++k) {
+        int K = 0;
+        const int root = recs[k].root;
+        if (root >= 0) {
+            const long o = k / max_cand * hw;
+            const int head = pc_id(mask, pxbase, o + root, 0);
+            K = max(d[succ[head]], 1);
+        }
+        nv[k] = K;
+        s += K;
+    }
+    part[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        int acc = 0;
+        for (int k = 0; k < 1024; ++k) { const int v = part[k]; part[k] = acc; acc += v; }
+        info[0] = acc;        // packed vertices
+        info[1] = hdr[0];     // cracks
+        info[2] = E;          // rounds run
+        info[3] = R;          // rounds launched
+    }
+    __syncthreads();
+    int acc = part[t];
+    for (long k = lo; k < hi; ++k) {
+        voff[k] = acc;
+        const int root = recs[k].root;
+        if (root >= 0) {
+            const long o = k / max_cand * hw;
+            const int head = pc_id(mask, pxbase, o + root, 0);
+            if (d[succ[head]] == 0) { verts[2L * acc] = (short)(root % W); verts[2L * acc + 1] = (short)(root / W); }
+        }
+        acc += nv[k];
+    }
+}
+
+// every kept vertex to its place: index (K - d + 1) mod K, d = weight from it to the head (the start pixel's vertex,
+// the last in rank order, is index 0)
+__global__ void crack_out_kernel(const int* __restrict__ hdr, int R, int W, const int* __restrict__ ckey, const int* __restrict__ ccand,
+                                 const unsigned char* __restrict__ wflag, const int* __restrict__ dA, const int* __restrict__ dB,
+                                 const int* __restrict__ nv, const int* __restrict__ voff, short* __restrict__ verts) {
+    const long total = hdr[0];
+    const int E = pc_rounds(hdr + 1, R);
+    const int* d = (E - 1) % 2 == 0 ? dB : dA;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        if (!(wflag[i] & 1)) continue;
+        const int c = ccand[i], K = nv[c], di = d[i];
+        if (di < 1 || di > K) continue;  // (cannot happen: 1 <= d <= K for a kept vertex)
+        const int idx = (K - di + 1) % K, p = ckey[i] >> 2;
+        const long at = 2L * ((long)voff[c] + idx);
+        verts[at] = (short)(p % W);
+        verts[at + 1] = (short)(p / W);
+    }
+}
+
 // ---- host stage ----------------------------------------------------------------------------------------------------
 struct Corners { float x[4], y[4]; };
 
@@ -514,6 +779,103 @@ float fixed_mean(long long hi, long long lo, long long count) {
     const float f = (float)(q | (rem != 0 ? 1 : 0));
     const float v = ldexpf(f, -(56 + sh));
     return neg ? -v : v;
+}
+
+// the same mean rounded once to fp64 (the polygon path's score: cv2.mean returns a double)
+double fixed_mean64(long long hi, long long lo, long long count) {
+    if (count <= 0) return 0.0;
+    const __int128 T = (__int128)hi * ((__int128)1 << 32) + lo;
+    if (T == 0) return 0.0;
+    const bool neg = T < 0;
+    const unsigned __int128 A = neg ? (unsigned __int128)(-T) : (unsigned __int128)T;
+    int top = 127;
+    while (!((A >> top) & 1)) --top;
+    const int sh = 125 - top;  // the quotient keeps >= 97 bits: bit 0 as the sticky bit rounds once
+    const unsigned __int128 num = A << sh;
+    const unsigned __int128 q = num / (unsigned __int128)count, rem = num % (unsigned __int128)count;
+    const double f = (double)(q | (rem != 0 ? 1 : 0));
+    const double v = ldexp(f, -(56 + sh));
+    return neg ? -v : v;
+}
+
+struct IP { int x, y; };
+
+// approxPolyDP(src, eps, closed) as OpenCV 4.x approx.cpp reads: squared eps; the initial split from three passes of
+// "farthest point from the last one" (first strict maximum); a stack of slices, each accepted (its start point
+// written) when max |cross|^2 <= eps^2 |d|^2, else split at the first strict maximum (right half pushed first); then
+// one in-place clean-up pass.  All coordinates are integers, so every product below is exact in fp64.
+std::vector<IP> approx_poly_dp(const std::vector<IP>& src, double eps) {
+    const int count = (int)src.size();
+    std::vector<IP> dst;
+    if (count == 0) return dst;
+    eps *= eps;
+    int pos = 0, rs = 0;
+    bool le_eps = false;
+    for (int it = 0; it < 3; ++it) {
+        pos = (pos + rs) % count;
+        const IP st = src[pos];
+        double max_dist = 0;
+        for (int j = 1; j < count; ++j) {
+            const IP pt = src[(pos + j) % count];
+            const double dx = pt.x - st.x, dy = pt.y - st.y, d = dx * dx + dy * dy;
+            if (d > max_dist) { max_dist = d; rs = j; }
+        }
+        le_eps = max_dist <= eps;
+    }
+    std::vector<std::pair<int, int>> stack;
+    if (!le_eps) {
+        const int s0 = pos % count, e0 = (rs + s0) % count;
+        stack.push_back({e0, s0});
+        stack.push_back({s0, e0});
+    } else {
+        dst.push_back(src[pos]);
+    }
+    while (!stack.empty()) {
+        const int a = stack.back().first, e = stack.back().second;
+        stack.pop_back();
+        const IP ep = src[e], sp = src[a];
+        int p = (a + 1) % count, split = -1;
+        bool le = true;
+        if (p != e) {
+            const double dx = ep.x - sp.x, dy = ep.y - sp.y;
+            double max_dist = 0;
+            while (p != e) {
+                const IP pt = src[p];
+                const double d = fabs((pt.y - sp.y) * dx - (pt.x - sp.x) * dy);
+                if (d > max_dist) { max_dist = d; split = p; }
+                p = (p + 1) % count;
+            }
+            le = max_dist * max_dist <= eps * (dx * dx + dy * dy);
+        }
+        if (le) dst.push_back(sp);
+        else { stack.push_back({split, e}); stack.push_back({a, split}); }
+    }
+    // clean-up: drop a point on an [almost] straight line between its neighbours (reads may see the pass's own writes)
+    const int cnt = (int)dst.size();
+    int new_count = cnt, rpos = cnt - 1;
+    auto rd = [&]() { const IP v = dst[rpos]; if (++rpos >= cnt) rpos = 0; return v; };
+    IP start = rd();
+    int wpos = rpos;
+    IP pt = rd();
+    for (int i = 0; i < cnt && new_count > 2; ++i) {
+        const IP end = rd();
+        const double dx = end.x - start.x, dy = end.y - start.y;
+        const double dist = fabs((pt.x - start.x) * dy - (pt.y - start.y) * dx);
+        const double inner = (double)(pt.x - start.x) * (end.x - pt.x) + (double)(pt.y - start.y) * (end.y - pt.y);
+        if (dist * dist <= 0.5 * eps * (dx * dx + dy * dy) && dx != 0 && dy != 0 && inner >= 0) {
+            --new_count;
+            dst[wpos] = start = end;
+            if (++wpos >= cnt) wpos = 0;
+            pt = rd();
+            ++i;
+            continue;
+        }
+        dst[wpos] = start = pt;
+        if (++wpos >= cnt) wpos = 0;
+        pt = end;
+    }
+    dst.resize(new_count);
+    return dst;
 }
 
 }  // namespace
@@ -620,6 +982,158 @@ int dbn_detect_host(const void* recs, const int* counts, int N, int max_candidat
         }
     }
     return DBN_OK;
+}
+
+// ---- polygons ------------------------------------------------------------------------------------------------------
+// contour workspace: per pixel mask (1 B) + first crack id (4 B); per crack slot (N (2HW + H + W), every unit edge of
+// the pixel grid) succ, key, candidate, predecessor pixel, 2 x (next, weight) (4 B each) + flags (1 B); rows; header
+static long pc_cracks(int N, int H, int W) { return (long)N * (2L * H * W + H + W); }
+
+long dbn_detect_poly_ws_bytes(int N, int H, int W, int max_candidates) {
+    if (N <= 0 || H <= 0 || W <= 0 || max_candidates <= 0) return -1;
+    const long px = (long)N * H * W, B = pc_cracks(N, H, W);
+    auto al = [](long b) { return (b + 255) / 256 * 256; };
+    return al(px) + al(4 * px) + 2 * al(4L * N * H) + al(4 * (1 + PC_MAX_ROUNDS)) + 8 * al(4 * B) + al(B);
+}
+
+long dbn_detect_poly_verts_cap(int N, int H, int W) {
+    if (N <= 0 || H <= 0 || W <= 0) return -1;
+    return pc_cracks(N, H, W);
+}
+
+int dbn_detect_poly(const float* pred, int N, int channels, int H, int W, float thresh, int max_candidates, void* ws, void* poly_ws,
+                    int* labels, void* table, short* verts, void* stream) {
+    DBN_REQUIRE(poly_ws && table && verts);
+    DBN_REQUIRE(pc_cracks(N, H, W) < (1L << 31) && (long)N * max_candidates < (1L << 31));
+    const int rc = dbn_detect(pred, N, channels, H, W, thresh, max_candidates, ws, labels, table, (int*)((char*)table + 72L * N * max_candidates),
+                              stream);
+    if (rc != DBN_OK) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    const long hw = (long)H * W, px = (long)N * hw, c = (long)N * max_candidates, B = pc_cracks(N, H, W);
+    auto al = [](long b) { return (b + 255) / 256 * 256; };
+    // dbn_detect's workspace: L, bitmap, acc, edge, slot (its layout)
+    char* q = (char*)ws;
+    q += al(4 * px);
+    const unsigned char* bitmap = (const unsigned char*)q; q += al(px);
+    q += al(24 * px);
+    const int* edge = (const int*)q; q += al(4 * px);
+    const int* slot = (const int*)q;
+    char* p = (char*)poly_ws;
+    unsigned char* mask = (unsigned char*)p; p += al(px);
+    int* pxbase = (int*)p; p += al(4 * px);
+    int* rowcnt = (int*)p; p += al(4L * N * H);
+    int* rowbase = (int*)p; p += al(4L * N * H);
+    int* hdr = (int*)p; p += al(4 * (1 + PC_MAX_ROUNDS));
+    int* succ = (int*)p; p += al(4 * B);
+    int* ckey = (int*)p; p += al(4 * B);
+    int* ccand = (int*)p; p += al(4 * B);
+    int* prevpix = (int*)p; p += al(4 * B);
+    int* nA = (int*)p; p += al(4 * B);
+    int* dA = (int*)p; p += al(4 * B);
+    int* nB = (int*)p; p += al(4 * B);
+    int* dB = (int*)p; p += al(4 * B);
+    unsigned char* wflag = (unsigned char*)p;
+    // table: recs [c] | counts [N] | nv [c] | voff [c] | info [4]
+    int* nv = (int*)((char*)table + 72L * c + 4L * N);
+    int* voff = nv + c;
+    int* info = voff + c;
+    const Rec* recs = (const Rec*)table;
+    int R = 1;  // rounds: 2^R >= the cracks of one image >= the longest cycle
+    while ((1L << R) < B / N && R < PC_MAX_ROUNDS) ++R;
+    const int G = dbn_grid(B, 256, 8192);
+    hipLaunchKernelGGL(crack_count_kernel, dim3(H, N), dim3(256), 0, st, bitmap, labels, edge, slot, H, W, rowcnt);
+    hipLaunchKernelGGL(crack_scan_kernel, dim3(1), dim3(1024), 0, st, rowcnt, (long)N * H, rowbase, hdr);
+    hipLaunchKernelGGL(crack_emit_kernel, dim3(H, N), dim3(256), 0, st, bitmap, labels, edge, slot, H, W, rowbase, mask, pxbase);
+    hipLaunchKernelGGL(crack_link_kernel, dim3(H, N), dim3(256), 0, st, bitmap, labels, slot, H, W, max_candidates, mask, pxbase, succ, ckey,
+                       ccand, prevpix, wflag);
+    hipLaunchKernelGGL(crack_weight_kernel, dim3(G), dim3(256), 0, st, hdr, W, succ, ckey, prevpix, wflag, nA, dA);
+    for (int r = 0; r < R; ++r) {
+        const bool ev = r % 2 == 0;
+        hipLaunchKernelGGL(crack_jump_kernel, dim3(G), dim3(256), 0, st, hdr, r, ev ? nA : nB, ev ? dA : dB, ev ? nB : nA, ev ? dB : dA, hdr + 1);
+    }
+    hipLaunchKernelGGL(cand_verts_kernel, dim3(1), dim3(1024), 0, st, recs, c, W, hw, max_candidates, hdr, R, mask, pxbase, succ, dA, dB, nv,
+                       voff, info, verts);
+    hipLaunchKernelGGL(crack_out_kernel, dim3(G), dim3(256), 0, st, hdr, R, W, ckey, ccand, wflag, dA, dB, nv, voff, verts);
+    return dbn_status();
+}
+
+int dbn_detect_poly_host(const void* recs, const int* counts, const int* nv, const int* voff, const short* verts, int N, int max_candidates,
+                         int H, int W, const double* params, const int* dest_hw, int* poly_n, int* poly_off, int* poly_xy, int poly_cap,
+                         int* poly_total, double* scores, double* info, int* approx_xy) {
+    DBN_REQUIRE(recs && counts && nv && voff && verts && params && dest_hw && poly_n && poly_off && poly_total && scores);
+    DBN_REQUIRE(N > 0 && max_candidates > 0 && H > 0 && W > 0 && poly_cap >= 0 && (poly_cap == 0 || poly_xy));
+    const double box_thresh = params[0], unclip_ratio = params[1];
+    const Rec* R = (const Rec*)recs;
+    std::vector<int> off(4096);
+    long total = 0;
+    for (int n = 0; n < N; ++n) {
+        DBN_REQUIRE(counts[n] >= 0 && dest_hw[2 * n] >= 0 && dest_hw[2 * n + 1] >= 0);
+        const int K = std::min(counts[n], max_candidates);
+        const double dw = (double)dest_hw[2 * n + 1], dh = (double)dest_hw[2 * n];
+        for (int k = 0; k < max_candidates; ++k) {
+            const long o = (long)n * max_candidates + k;
+            poly_n[o] = 0;
+            poly_off[o] = (int)std::min(total, (long)INT_MAX);
+            scores[o] = 0.0;
+            if (info) { info[4 * o] = 0; info[4 * o + 1] = 0; info[4 * o + 2] = 0; info[4 * o + 3] = -1; }
+            if (k >= K) continue;
+            const Rec& r = R[o];
+            const int nc = nv[o];
+            DBN_REQUIRE(nc >= 1 && voff[o] >= 0);
+            const short* cv = verts + 2L * voff[o];
+            std::vector<IP> c(nc);
+            long a = 0, b = 0;  // axis and diagonal steps: cv2.arcLength without its summation order
+            for (int i = 0; i < nc; ++i) {
+                c[i] = {cv[2 * i], cv[2 * i + 1]};
+                const int j = i + 1 == nc ? 0 : i + 1;
+                const int dx = abs(cv[2 * j] - cv[2 * i]), dy = abs(cv[2 * j + 1] - cv[2 * i + 1]);
+                if (dx == 0 || dy == 0) a += dx + dy;
+                else b += dx;
+            }
+            const double len = (double)a + (double)b * sqrt(2.0);
+            const std::vector<IP> ap = approx_poly_dp(c, 0.005 * len);
+            const double score = fixed_mean64(r.sum_hi, r.sum_lo, r.count);
+            if (info) { info[4 * o] = score; info[4 * o + 1] = (double)ap.size(); }
+            if (approx_xy)
+                for (size_t i = 0; i < ap.size(); ++i) { approx_xy[2 * (voff[o] + i)] = ap[i].x; approx_xy[2 * (voff[o] + i) + 1] = ap[i].y; }
+            if (ap.size() < 4) continue;
+            if (box_thresh > score) continue;
+            const int m = (int)ap.size();
+            std::vector<double> xs(m), ys(m), xy(2 * m);
+            for (int i = 0; i < m; ++i) { xs[i] = ap[i].x; ys[i] = ap[i].y; xy[2 * i] = xs[i]; xy[2 * i + 1] = ys[i]; }
+            const double distance = ring_area(xs.data(), ys.data(), m) * unclip_ratio / ring_length(xs.data(), ys.data(), m);
+            int cnt = 0, paths = 0;
+            int rc = dbn_poly_offset_paths(xy.data(), m, &distance, off.data(), (int)off.size() / 2, &cnt, &paths);
+            if (rc != DBN_OK && cnt > (int)off.size() / 2) {
+                off.resize(2 * (size_t)cnt);
+                rc = dbn_poly_offset_paths(xy.data(), m, &distance, off.data(), cnt, &cnt, &paths);
+            }
+            if (rc != DBN_OK) return rc;
+            if (info) info[4 * o + 2] = paths;
+            if (paths > 1) continue;  // the reference skips an offset of several paths (pieces or holes)
+            double sside = -1;  // get_mini_boxes of an empty path
+            if (cnt > 0) {
+                std::vector<std::pair<long long, long long>> pts(cnt);
+                for (int i = 0; i < cnt; ++i) pts[i] = {off[2 * i + 1], off[2 * i]};
+                rect_corners(min_area_rect(pts), &sside);
+            }
+            if (info) info[4 * o + 3] = sside;
+            if (sside < 5) continue;
+            poly_n[o] = cnt;
+            for (int i = 0; i < cnt; ++i, ++total) {  // np.clip(np.round(v / size * dest), 0, dest) in fp64 on int64
+                if (total >= poly_cap) continue;
+                double vx = rint((double)off[2 * i] / (double)W * dw), vy = rint((double)off[2 * i + 1] / (double)H * dh);
+                vx = vx < 0 ? 0 : vx > dw ? dw : vx;
+                vy = vy < 0 ? 0 : vy > dh ? dh : vy;
+                poly_xy[2 * total] = (int)vx;
+                poly_xy[2 * total + 1] = (int)vy;
+            }
+            scores[o] = score;
+        }
+    }
+    DBN_REQUIRE(total < INT_MAX);
+    *poly_total = (int)total;
+    return total > poly_cap ? DBN_ERR_ARG : DBN_OK;
 }
 
 }  // extern "C"

@@ -256,8 +256,9 @@ int winding(const std::vector<IPt>& p, double x, double y) {  // nonzero winding
 // the region of winding number > 0; that region's boundary is traced here from the path's arrangement: every edge is split
 // at every crossing, a piece is kept when the winding number changes from <= 0 to > 0 across it (oriented with the
 // region on its left), and kept pieces, with end points rounded to integers as Clipper rounds its intersections, are
-// linked into loops.  Returns the loops of positive area (outer boundaries; holes dropped).
-std::vector<std::vector<IPt>> positive_region(const std::vector<IPt>& p) {
+// linked into loops.  Returns the loops of positive area (outer boundaries); holes, the loops of negative area, are
+// dropped and counted in *holes when it is given.
+std::vector<std::vector<IPt>> positive_region(const std::vector<IPt>& p, int* holes = nullptr) {
     const int n = (int)p.size();
     struct Edge { IPt a, b; };
     std::vector<Edge> kept;
@@ -341,7 +342,10 @@ std::vector<std::vector<IPt>> positive_region(const std::vector<IPt>& p) {
                 if (cross(b.x - a.x, b.y - a.y, c.x - b.x, c.y - b.y) == 0) { loop.erase(loop.begin() + i); changed = true; --i; }
             }
         }
-        if (loop.size() >= 3 && clip_area(loop) > 0) loops.push_back(loop);
+        if (loop.size() < 3) continue;
+        const double a = clip_area(loop);
+        if (a > 0) loops.push_back(loop);
+        else if (a < 0 && holes) ++*holes;
     }
     return loops;
 }
@@ -368,7 +372,9 @@ int dbn_normalize_u8(const unsigned char* in, int N, int H, int W, float m0, flo
     return dbn_status();
 }
 
-int dbn_poly_offset(const double* xy, int n, const double* delta, int* out_xy, int cap, int* out_n) {
+// the offset of dbn_poly_offset: the piece of largest area, and the number of paths Clipper's Execute returns (outer
+// loops and holes)
+static int poly_offset(const double* xy, int n, const double* delta, int* out_xy, int cap, int* out_n, int* out_paths) {
     DBN_REQUIRE(xy && delta && out_n && n >= 0 && cap >= 0 && (cap == 0 || out_xy));
     std::vector<IPt> path(n);
     for (int i = 0; i < n; ++i) {
@@ -378,17 +384,31 @@ int dbn_poly_offset(const double* xy, int n, const double* delta, int* out_xy, i
     DBN_REQUIRE(isfinite(*delta));
     const std::vector<IPt> raw = raw_offset(path, *delta);
     std::vector<IPt> best;
+    int paths = 0;
     if (!raw.empty()) {
         double best_area = 0;
-        for (const auto& l : positive_region(raw)) {  // several pieces: the one of largest area (ties: the first traced)
+        int holes = 0;
+        const std::vector<std::vector<IPt>> loops = positive_region(raw, &holes);
+        for (const auto& l : loops) {  // several pieces: the one of largest area (ties: the first traced)
             const double a = clip_area(l);
             if (a > best_area) { best_area = a; best = l; }
         }
+        paths = (int)loops.size() + holes;
     }
+    if (out_paths) *out_paths = paths;
     *out_n = (int)best.size();
     if ((int)best.size() > cap) return DBN_ERR_ARG;
     for (size_t i = 0; i < best.size(); ++i) { out_xy[2 * i] = (int)best[i].x; out_xy[2 * i + 1] = (int)best[i].y; }
     return DBN_OK;
+}
+
+int dbn_poly_offset(const double* xy, int n, const double* delta, int* out_xy, int cap, int* out_n) {
+    return poly_offset(xy, n, delta, out_xy, cap, out_n, nullptr);
+}
+
+int dbn_poly_offset_paths(const double* xy, int n, const double* delta, int* out_xy, int cap, int* out_n, int* out_paths) {
+    DBN_REQUIRE(out_paths);
+    return poly_offset(xy, n, delta, out_xy, cap, out_n, out_paths);
 }
 
 }  // extern "C"

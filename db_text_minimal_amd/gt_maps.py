@@ -93,6 +93,24 @@ def offset_polygon(poly, delta):
         return out[:n[0]].astype(np.int64)
 
 
+def offset_polygon_paths(poly, delta):
+    """offset_polygon plus the number of paths Clipper's Execute returns, outer loops and holes
+    (dbn_poly_offset_paths): (int64 [K, 2] piece of largest area, paths)."""
+    xy = np.ascontiguousarray(np.asarray(poly, dtype=np.float64).reshape(-1, 2))
+    d = np.array([float(delta)], np.float64)
+    n = np.zeros(1, np.int32)
+    paths = np.zeros(1, np.int32)
+    cap = 1024
+    while True:
+        out = np.zeros((cap, 2), np.int32)
+        rc = lib().dbn_poly_offset_paths(xy.ctypes.data, len(xy), d.ctypes.data, out.ctypes.data, cap, n.ctypes.data, paths.ctypes.data)
+        if rc == 1 and n[0] > cap:
+            cap = int(n[0])
+            continue
+        check(rc, 'poly_offset_paths')
+        return out[:n[0]].astype(np.int64), int(paths[0])
+
+
 def _bbox(pts):
     return int(pts[:, 0].min()), int(pts[:, 0].max()), int(pts[:, 1].min()), int(pts[:, 1].max())
 

@@ -16,7 +16,11 @@ Text boxes without OpenCV or pyclipper (csrc/detect.hip):
   detect_boxes(preds, ...)          boxes_from_bitmap (postprocess.py:105-141, is_output_polygon=False) for a batch:
                                     per image int16 boxes [K, 4, 2] and fp32 scores [K], K = min(#candidates,
                                     max_candidates), skipped rows zero.  The map never leaves the device.
-  SegDetectorRepresenter            the reference's class over detect_boxes (polygon output: NotImplementedError)
+  detect_polygons(preds, ...)       polygons_from_bitmap (postprocess.py:54-103, is_output_polygon=True) for a batch:
+                                    per image a list of int64 [P, 2] polygons and a list of float scores, kept
+                                    candidates only.  detect_contours is its device stage, detect_poly_host its host stage.
+  SegDetectorRepresenter            the reference's class: __call__ over detect_boxes, .polygons over detect_polygons
+                                    (__call__(..., is_output_polygon=True) still raises NotImplementedError)
 
 Semantics.  A candidate is a foreground component of `pred[n, 0] > thresh`, 8-connected: the region one outer border
 of cv2.findContours encloses.  Candidates come in DESCENDING raster order of their first pixel (cv2's RETR_LIST
@@ -30,6 +34,20 @@ length (shapely's formulas) with the Clipper restatement of gt_maps.offset_polyg
 unclipped points, skip if its shorter side < 5; order R2 and scale to dest size in fp32 with half-to-even rounding.
 PARITY UNPINNED against cv2 / pyclipper: R1 / R2 corners come from exact integer calipers, not cv2's float
 minAreaRect, and unclip keeps the largest piece of the offset where pyclipper returns all of them.
+
+Polygons.  Same candidates, order and max_candidates truncation as the boxes; hole borders are
+NOT emitted (RETR_LIST would return them as candidates too).  Per candidate C: contour = C's outer border as
+cv2.findContours(RETR_LIST, CHAIN_APPROX_SIMPLE) traces it, from C's raster-first pixel, counter-clockwise on screen,
+keeping the pixels where the step direction changes.  The device traces every border at once: a crack is (pixel of C,
+side) with background or the frame across it, its successor is a function of a 2 x 2 block, and Wyllie pointer
+jumping ranks the cracks of each cycle from its head (the left crack of C's first pixel).  Host, as the reference:
+eps = 0.005 * arcLength (a + b sqrt(2) over a axis and b diagonal steps), approxPolyDP (OpenCV 4.x's closed-curve
+algorithm, fp64); skip if fewer than 4 points; score = mean of pred over filled(C) rounded once to fp64 (float32 of it
+is the box score), skip if box_thresh > score; unclip by area * unclip_ratio / length; skip if the offset has more
+than one path (pieces or holes); skip if the shorter side of its min-area rectangle is < 5 (-1 for an empty offset);
+scale the int64 vertices as clip(round(v / size * dest), 0, dest) in fp64, half to even.  PARITY UNPINNED against cv2
+/ pyclipper: approxPolyDP and arcLength rounding are restated, not checked against cv2; the offset is the Clipper
+restatement of gt_maps.offset_polygon.
 """
 import numpy as np
 import torch
@@ -130,8 +148,105 @@ def detect_boxes(preds, thresh=0.3, box_thresh=0.7, max_candidates=1000, unclip_
     return [(boxes[n, :K[n]].copy(), scores[n, :K[n]].copy()) for n in range(len(K))]
 
 
+def _poly_table_layout(N, M):
+    rec = N * M * REC_DTYPE.itemsize
+    return rec, rec + 4 * N, rec + 4 * N + 4 * N * M, rec + 4 * N + 8 * N * M, rec + 4 * N + 8 * N * M + 16
+
+
+def detect_contours(preds, thresh=0.3, max_candidates=1000, prefill=None):
+    """Device stage of detect_polygons, enqueued on the current stream: dbn_detect, then the outer border of every kept
+    candidate traced in parallel.  Returns dict(recs [N, M] REC_DTYPE, counts [N] int32, nv [N, M] int32 (compressed
+    vertices per candidate), voff [N, M] int32 (offsets into verts), verts int16 [V, 2] (x, y) packed over the batch,
+    info int32 [4] = (vertices, cracks, pointer-jumping rounds run, rounds launched)).  Two transfers: the fixed-size
+    table, then exactly the V vertices.  prefill: a byte value written over every workspace and output buffer first."""
+    assert preds.is_cuda and preds.dtype == torch.float32 and preds.dim() == 4, (preds.device, preds.dtype, preds.shape)
+    preds = preds.contiguous()
+    N, C, H, W = preds.shape
+    M = int(max_candidates)
+    assert M > 0
+    L = lib()
+    ws_bytes, pws_bytes, cap = L.dbn_detect_ws_bytes(N, H, W, M), L.dbn_detect_poly_ws_bytes(N, H, W, M), L.dbn_detect_poly_verts_cap(N, H, W)
+    if min(ws_bytes, pws_bytes, cap) < 0:
+        raise RuntimeError('libdbnet_hip: invalid argument in detect_poly_ws_bytes')
+    dev = preds.device
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    pws = torch.empty(pws_bytes, device=dev, dtype=torch.uint8)
+    labels = torch.empty((N, H, W), device=dev, dtype=torch.int32)
+    o_counts, o_nv, o_voff, o_info, size = _poly_table_layout(N, M)
+    table = torch.empty(size, device=dev, dtype=torch.uint8)
+    verts = torch.empty((cap, 2), device=dev, dtype=torch.int16)
+    if prefill is not None:
+        for t in (ws, pws, labels.view(torch.uint8), table, verts.view(torch.uint8)):
+            t.fill_(int(prefill))
+    check(L.dbn_detect_poly(preds.data_ptr(), N, C, H, W, float(thresh), M, ws.data_ptr(), pws.data_ptr(), labels.data_ptr(), table.data_ptr(),
+                            verts.data_ptr(), _stream(preds)), 'detect_poly')
+    host = table.cpu().numpy()
+    info = host[o_info:].view(np.int32).copy()
+    return dict(recs=host[:o_counts].view(REC_DTYPE).reshape(N, M), counts=host[o_counts:o_nv].view(np.int32).copy(),
+                nv=host[o_nv:o_voff].view(np.int32).reshape(N, M).copy(), voff=host[o_voff:o_info].view(np.int32).reshape(N, M).copy(),
+                verts=verts[:int(info[0])].cpu().numpy(), info=info)
+
+
+def contour_of(c, n, k):
+    """the compressed outer border of candidate k of image n from detect_contours' result: int64 [P, 2] (x, y)"""
+    o = int(c['voff'][n, k])
+    return c['verts'][o:o + int(c['nv'][n, k])].astype(np.int64)
+
+
+def detect_poly_host(c, H, W, box_thresh=0.7, unclip_ratio=1.5, dest_sizes=None, return_info=False):
+    """Host stage of detect_polygons (dbn_detect_poly_host, one call for the batch) on the result of detect_contours.
+    Returns per image (list of int64 [P, 2] polygons, list of float scores), kept candidates only[, info dict: score64,
+    n_approx, paths, sside as [N, M] arrays (paths 0 / sside -1 where the candidate was skipped first), approx (per
+    image, per candidate: int64 [A, 2] approxPolyDP vertices)]."""
+    recs = np.ascontiguousarray(c['recs'], dtype=REC_DTYPE)
+    N, M = recs.shape
+    counts = np.ascontiguousarray(c['counts'], dtype=np.int32)
+    nv, voff = np.ascontiguousarray(c['nv'], np.int32), np.ascontiguousarray(c['voff'], np.int32)
+    verts = np.ascontiguousarray(c['verts'], np.int16).reshape(-1, 2)
+    if len(verts) == 0:
+        verts = np.zeros((1, 2), np.int16)
+    dest = np.array([(H, W)] * N if dest_sizes is None else [(int(h), int(w)) for h, w in dest_sizes], dtype=np.int32).reshape(N, 2)
+    params = np.array([float(box_thresh), float(unclip_ratio)], np.float64)
+    pn, poff = np.zeros((N, M), np.int32), np.zeros((N, M), np.int32)
+    scores = np.zeros((N, M), np.float64)
+    info = np.zeros((N, M, 4), np.float64)
+    approx = np.zeros((max(len(verts), 1), 2), np.int32)
+    total = np.zeros(1, np.int32)
+    cap = 4096
+    while True:
+        pxy = np.zeros((cap, 2), np.int32)
+        rc = lib().dbn_detect_poly_host(recs.ctypes.data, counts.ctypes.data, nv.ctypes.data, voff.ctypes.data, verts.ctypes.data, N, M, H, W,
+                                        params.ctypes.data, dest.ctypes.data, pn.ctypes.data, poff.ctypes.data, pxy.ctypes.data, cap,
+                                        total.ctypes.data, scores.ctypes.data, info.ctypes.data, approx.ctypes.data)
+        if rc == 1 and total[0] > cap:
+            cap = int(total[0])
+            continue
+        check(rc, 'detect_poly_host')
+        break
+    res = []
+    for n in range(N):
+        K = min(int(counts[n]), M)
+        ks = [k for k in range(K) if pn[n, k] > 0]
+        res.append(([pxy[poff[n, k]:poff[n, k] + pn[n, k]].astype(np.int64) for k in ks], [float(scores[n, k]) for k in ks]))
+    if not return_info:
+        return res
+    K = np.minimum(counts, M)
+    ap = [[approx[voff[n, k]:voff[n, k] + int(info[n, k, 1])].astype(np.int64) for k in range(K[n])] for n in range(N)]
+    return res, dict(score64=info[..., 0].copy(), n_approx=info[..., 1].astype(np.int64), paths=info[..., 2].astype(np.int64),
+                     sside=info[..., 3].copy(), approx=ap)
+
+
+def detect_polygons(preds, thresh=0.3, box_thresh=0.7, max_candidates=1000, unclip_ratio=1.5, dest_sizes=None):
+    """polygons_from_bitmap of the reference (is_output_polygon=True) for every image of preds [N, C, H, W] (fp32 device
+    tensor, channel 0 = probability map).  dest_sizes: per image (height, width), default the map's.  Returns per image
+    (list of int64 [P, 2] polygons, list of float scores), the kept candidates only, as the reference."""
+    c = detect_contours(preds, thresh, max_candidates)
+    return detect_poly_host(c, preds.shape[2], preds.shape[3], box_thresh, unclip_ratio, dest_sizes)
+
+
 class SegDetectorRepresenter:
-    """The reference's SegDetectorRepresenter (postprocess.py:7-48) over detect_boxes; box output only."""
+    """The reference's SegDetectorRepresenter (postprocess.py:7-48): __call__ over detect_boxes (box output), .polygons
+    over detect_polygons (polygon output)."""
 
     def __init__(self, thresh=0.3, box_thresh=0.7, max_candidates=1000, unclip_ratio=1.5):
         self.min_size = 3
@@ -144,7 +259,14 @@ class SegDetectorRepresenter:
         """batch['shape'][i] = (height, width) of image i; pred [N, C, H, W] fp32 device tensor -> (boxes_batch,
         scores_batch), one (int16 [K, 4, 2], fp32 [K]) pair per image."""
         if is_output_polygon:
-            raise NotImplementedError('polygon output (approxPolyDP of traced contours) is not implemented')
+            raise NotImplementedError('is_output_polygon=True is not routed here: use SegDetectorRepresenter.polygons or detect_polygons')
         dest = [(int(h), int(w)) for h, w in batch['shape']]
         res = detect_boxes(pred, self.thresh, self.box_thresh, self.max_candidates, self.unclip_ratio, dest)
         return [b for b, _ in res], [s for _, s in res]
+
+    def polygons(self, batch, pred):
+        """The reference's __call__(batch, pred, is_output_polygon=True): (boxes_batch, scores_batch), per image a list
+        of int64 [P, 2] polygons and a list of float scores."""
+        dest = [(int(h), int(w)) for h, w in batch['shape']]
+        res = detect_polygons(pred, self.thresh, self.box_thresh, self.max_candidates, self.unclip_ratio, dest)
+        return [p for p, _ in res], [s for _, s in res]

@@ -416,6 +416,9 @@ int dbn_normalize_u8(const unsigned char* in, int N, int H, int W, float m0, flo
  * area to out_xy[*out_n][2] (*out_n = 0: the offset vanished); returns 1 with *out_n = the needed count if it exceeds
  * cap.  PARITY UNPINNED against pyclipper. */
 int dbn_poly_offset(const double* xy, int n, const double* delta, int* out_xy, int cap, int* out_n);
+/* host: dbn_poly_offset, and *out_paths = the number of paths Clipper's Execute returns (outer loops and holes; 0 when
+ * the offset vanishes).  dbn_poly_offset's own result is unchanged by it. */
+int dbn_poly_offset_paths(const double* xy, int n, const double* delta, int* out_xy, int cap, int* out_n, int* out_paths);
 
 /* ---- text boxes from probability maps: boxes_from_bitmap of postprocess.py:105-141 (csrc/detect.hip,
  *      db_text_minimal_amd/postprocess.py detect_boxes).  PARITY UNPINNED against cv2 / pyclipper. ---- */
@@ -441,6 +444,31 @@ int dbn_detect(const float* pred, int N, int channels, int H, int W, float thres
  * min side of R1, score of every candidate. */
 int dbn_detect_host(const void* recs, const int* counts, int N, int max_candidates, int H, int W, const double* params, const int* dest_hw,
                     short* boxes, float* scores, float* info);
+
+/* ---- text polygons: polygons_from_bitmap of postprocess.py:54-103 (csrc/detect.hip, db_text_minimal_amd/postprocess.py
+ *      detect_polygons).  PARITY UNPINNED against cv2 / pyclipper. ---- */
+/* bytes of the contour workspace dbn_detect_poly needs besides dbn_detect's (about 71 B per pixel) */
+long dbn_detect_poly_ws_bytes(int N, int H, int W, int max_candidates);
+/* capacity of the packed vertex buffer, in (x, y) int16 pairs: N * (2 H W + H + W), the unit edges of the pixel grid */
+long dbn_detect_poly_verts_cap(int N, int H, int W);
+/* Device stage: dbn_detect (ws: dbn_detect_ws_bytes, labels as there), then the outer border of every kept candidate,
+ * traced in parallel (cracks, successors, Wyllie pointer jumping, CHAIN_APPROX_SIMPLE compression).
+ * table: recs [N][max_candidates] dbn_detect_rec | counts [N] int | nv [N][max_candidates] int (compressed vertices of
+ * the candidate's outer border, 0 for an empty slot) | voff [N][max_candidates] int (offset of its first vertex in
+ * verts) | info [4] int {total vertices, cracks, pointer-jumping rounds run, rounds launched}.
+ * verts: dbn_detect_poly_verts_cap pairs; the first info[0] are written, (x, y) int16, per candidate from its
+ * raster-first pixel, counter-clockwise on screen.  poly_ws: dbn_detect_poly_ws_bytes, any contents. */
+int dbn_detect_poly(const float* pred, int N, int channels, int H, int W, float thresh, int max_candidates, void* ws, void* poly_ws,
+                    int* labels, void* table, short* verts, void* stream);
+/* host: postprocess.py:72-101 on the table and vertices of dbn_detect_poly (host memory).  params = {box_thresh,
+ * unclip_ratio} (fp64), dest_hw[N][2] = (height, width) to scale to.  Per slot: poly_n (0: skipped), poly_off (first
+ * vertex in poly_xy), the scaled unclipped polygon as int32 (x, y) pairs in poly_xy, scores fp64 (0: skipped).
+ * Returns 1 with *poly_total = the vertices needed when they exceed poly_cap.  info (NULL or [N][max_candidates][4]
+ * fp64): score, approxPolyDP vertices, offset paths, shorter side of the unclipped min-area rectangle (-1: not reached);
+ * approx_xy (NULL or info[0] int32 pairs): the approxPolyDP vertices, at voff. */
+int dbn_detect_poly_host(const void* recs, const int* counts, const int* nv, const int* voff, const short* verts, int N, int max_candidates,
+                         int H, int W, const double* params, const int* dest_hw, int* poly_n, int* poly_off, int* poly_xy, int poly_cap,
+                         int* poly_total, double* scores, double* info, int* approx_xy);
 
 
 /* =====================================================================================================================

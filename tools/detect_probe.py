@@ -1,13 +1,21 @@
 """Time detect_boxes (csrc/detect.hip + dbn_detect_host) on synthetic probability maps.
 
     python tools/detect_probe.py [--reps 10] [--out profiles/r08_detect_probe.txt]
+    python tools/detect_probe.py --poly [--reps 10] [--out profiles/r09_detect_poly_probe.txt]
 
 For 16 x 640^2 and 32 x 1280^2 maps of each kind (about 50 text blobs per image; a spiral; a checkerboard) it reports
   device   median time of the dbn_detect launch sequence (HIP events on the current stream, buffers preallocated)
   host     median wall time of the host stage (dbn_detect_host, one call per batch)
   floor    one pass over the fp32 probability map (channel 0) at 8 TB/s, and the device stage's own bytes per pixel
   d2h      bytes copied to the host (records + counts) against the 4 B/px fp32 map the host route copies
-No target is set: these are the first numbers for this path."""
+No target is set: these are the first numbers for this path.
+
+--poly times detect_polygons (dbn_detect_poly + dbn_detect_poly_host) on the same maps instead:
+  contour  median time of dbn_detect_poly minus median time of dbn_detect: the contour launches alone
+  rounds   pointer-jumping rounds run / launched, cracks and compressed vertices per image
+  host     median wall time of the host stage (dbn_detect_poly_host, one call per batch)
+  d2h      bytes of the two copies: the fixed-size table, then exactly the packed vertices
+  serial   for the spiral: a serial walk's estimate for its one border, at 94-250 ns per dependent step"""
 import argparse
 import math
 import os
@@ -119,15 +127,75 @@ def probe(kind, N, S, reps, M=1000):
                                                              map_bytes / 1e6))
 
 
+def timed(launch, reps):
+    for _ in range(2):
+        launch()
+    torch.cuda.synchronize()
+    dev = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        launch()
+        b.record()
+        b.synchronize()
+        dev.append(a.elapsed_time(b) * 1e3)
+    return statistics.median(dev)
+
+
+def probe_poly(kind, N, S, reps, M=1000):
+    rng = np.random.default_rng(0)
+    preds = make(kind, N, S, rng)
+    L = lib()
+    ws = torch.empty(L.dbn_detect_ws_bytes(N, S, S, M), device='cuda', dtype=torch.uint8)
+    pws = torch.empty(L.dbn_detect_poly_ws_bytes(N, S, S, M), device='cuda', dtype=torch.uint8)
+    labels = torch.empty((N, S, S), device='cuda', dtype=torch.int32)
+    o_counts, o_nv, o_voff, o_info, size = P._poly_table_layout(N, M)
+    table = torch.empty(size, device='cuda', dtype=torch.uint8)
+    verts = torch.empty((L.dbn_detect_poly_verts_cap(N, S, S), 2), device='cuda', dtype=torch.int16)
+    st = torch.cuda.current_stream().cuda_stream
+
+    def launch_detect():
+        check(L.dbn_detect(preds.data_ptr(), N, 2, S, S, 0.3, M, ws.data_ptr(), labels.data_ptr(), table.data_ptr(), table.data_ptr() + o_counts,
+                           st), 'detect')
+
+    def launch_poly():
+        check(L.dbn_detect_poly(preds.data_ptr(), N, 2, S, S, 0.3, M, ws.data_ptr(), pws.data_ptr(), labels.data_ptr(), table.data_ptr(),
+                                verts.data_ptr(), st), 'detect_poly')
+
+    t_det = timed(launch_detect, reps)
+    t_poly = timed(launch_poly, reps)
+    host = table.cpu().numpy()
+    info = host[o_info:].view(np.int32).copy()
+    c = dict(recs=host[:o_counts].view(P.REC_DTYPE).reshape(N, M), counts=host[o_counts:o_nv].view(np.int32).copy(),
+             nv=host[o_nv:o_voff].view(np.int32).reshape(N, M).copy(), voff=host[o_voff:o_info].view(np.int32).reshape(N, M).copy(),
+             verts=verts[:int(info[0])].cpu().numpy())
+    hst = []
+    for _ in range(max(3, reps // 2)):
+        t0 = time.perf_counter()
+        res = P.detect_poly_host(c, S, S)
+        hst.append((time.perf_counter() - t0) * 1e6)
+    kept = sum(len(r[0]) for r in res)
+    d2h = size + 4 * int(info[0])
+    line = ('%-8s %2d x %4d^2  detect %9.1f us  poly %9.1f us  contour %9.1f us  rounds %2d/%2d  cracks/img %8d  verts/img %7d  '
+            'host %9.1f us  polygons %5d  | d2h %.2f MB + %.2f MB' % (kind, N, S, t_det, t_poly, t_poly - t_det, info[2], info[3], info[1] // N,
+                                                                 info[0] // N, statistics.median(hst), kept, size / 1e6,
+                                                                 4 * int(info[0]) / 1e6))
+    if kind == 'spiral':
+        longest = int(info[1]) // N  # one candidate per image
+        line += '  | serial walk of its border: %.0f-%.0f ms per image' % (longest * 94e-6, longest * 250e-6)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=10)
+    ap.add_argument('--poly', action='store_true', help='time detect_polygons instead of detect_boxes')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
-    lines = ['detect_probe: median of %d launches; %s' % (a.reps, torch.cuda.get_device_name(0))]
+    lines = ['detect_probe%s: median of %d launches; %s' % (' --poly' if a.poly else '', a.reps, torch.cuda.get_device_name(0))]
     for N, S in ((16, 640), (32, 1280)):
         for kind in ('blobs', 'spiral', 'checker'):
-            lines.append(probe(kind, N, S, a.reps))
+            lines.append(probe_poly(kind, N, S, a.reps) if a.poly else probe(kind, N, S, a.reps))
             print(lines[-1], flush=True)
     if a.out:
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
