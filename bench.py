@@ -2,7 +2,7 @@
 """Headline benchmark: DBNet (ResNet18-FPN-DBHead) training images/s at 640x640, bs 16 per GPU,
 fp32, synthetic data (BASELINE.json `metric`, configs[1]; the path of SURVEY.md §8).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A step is one iteration of the reference's loop (train.py:160-172): forward, DBLoss,
 backward, [one RCCL all-reduce of the flat gradients when N > 1], Adam — all HIP kernels of
@@ -11,19 +11,27 @@ torch.distributed.run environment (WORLD_SIZE unset) this script starts `python 
 bench.py ...` itself as a fresh child process (before anything here touches the GPU), forwards rank 0's ONE JSON line and exits
 with the child's code; fewer than N visible GPUs -> exit code 2.  Launched BY torch.distributed.run it is one of the N ranks.
 
-Extra objects on the JSON line:
-  roofline      the dominant kernel (the MFMA kernel — implicit-GEMM conv or weight gradient — with the largest share
-                of the step): algorithmic FLOP/s from HIP-event brackets around its launches inside the timed
-                region, vs the MFMA peak of the conv math in use (157.3 TFLOP/s for exact fp32)
-  kernels       the same figure for every igemm tile variant, the weight-gradient kernels and the
-                HBM-bound DB-head kernels (instrumented extra step after the timed region)
+A plain run sets up, takes the W warm-up and the K timed steps, writes --dump-outputs and prints the line: the headline
+(`value`, `ms_per_step`) and what the timed region itself recorded —
+  timing        per-step HIP-event times and host enqueue times of the K steps
+  engine_clock  the shader clock sampled beside every timed step
   roofline_hbm  the DB-head group (head tail forward / backward, DBLoss forward / backward) against the HBM peak: on the
                 fused kernels' own bytes and on SURVEY section 8d's unfused-algorithmic 84 B/px
-  cpu_baseline  the CPU oracle (oracle/dbnet_oracle.py, plain PyTorch fp32) timed on this host
   dump_outputs  with --dump-outputs DIR: the arrays of the LAST timed step written to DIR (see dump_outputs below)
+The timed region is the same with and without --full (its instrumented steps included), so is the headline.
+
+--full adds what takes steps or runs of its own (`"full": true` on the line):
   parity        BEFORE the timed region: one step of the benchmarked configuration on the inputs of tests/golden/cfg2_16x640.npz
                 (the reference's own train step at 16x3x640x640) — distances of the three maps and the five losses from the
                 reference's numbers; the run exits non-zero above the north_star tolerance
+  roofline      the dominant kernel (the MFMA kernel — implicit-GEMM conv or weight gradient — with the largest share
+                of the step): algorithmic FLOP/s from HIP-event brackets around its launches inside the timed
+                region, vs the MFMA peak of the conv math in use (157.3 TFLOP/s for exact fp32) and the sustained MFMA rate
+  kernels       the same figure for every igemm tile variant, the weight-gradient kernels and the
+                HBM-bound DB-head kernels (instrumented extra steps after the timed region)
+  data_parallel N > 1: the other exchange form timed, and the replicas' parameter checksum (exit non-zero on divergence)
+  alt_modes     the other conv-math modes timed
+  cpu_baseline  the CPU oracle (oracle/dbnet_oracle.py, plain PyTorch fp32) timed on this host
 """
 import argparse
 import json
@@ -341,6 +349,15 @@ def launched_by():
     return 'torch.distributed.run (external)' if 'WORLD_SIZE' in os.environ else 'single process'
 
 
+def finish(rank, line):
+    """Rank 0 prints the ONE JSON line; every rank leaves the process group."""
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
+
+
 def hbm_group(summ, px, steps):
     """The DB-head group of BASELINE's metric ("DB-head GB/s vs HBM peak"): head tail forward / backward (+ its fold launches),
     DBLoss forward (+ finalize) / backward, from a KernelTimer summary over `steps` instrumented steps.  `achieved` is on the
@@ -371,7 +388,13 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=16, help='images per GPU (BASELINE: 16)')
     ap.add_argument('--size', type=int, default=640)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline, measure and check everything else: parity gate, serial per-kernel steps, rooflines, '
+                         'sustained MFMA rate, other exchange form (N > 1), other conv-math modes, CPU baseline.  --serial-steps, '
+                         '--no-alt-modes, --no-parity and --no-cpu-baseline select parts of this run and imply it')
+    # (these four default to None so that giving one can be told apart from not giving it: a command line written for the
+    # extras before --full existed still gets them)
+    ap.add_argument('--no-cpu-baseline', action='store_true', default=None)
     ap.add_argument('--math', default='f32', choices=['f32', 'bf16x3', 'bf16', 'bf16c'],
                     help="precision mode: f32 = exact-fp32 MFMA (default, BASELINE configs[1]); bf16x3 = fp32-accurate split; "
                          "bf16 = native bf16 storage + MFMA (BASELINE configs[2]); bf16c = fp32 tensors, bf16 operands")
@@ -384,16 +407,21 @@ def main():
                     help='replay forward + loss + backward as one hipGraph (DBTrainer.use_graph) instead of launching every kernel '
                          'individually.  Measured SLOWER on ROCm 7.2 / MI355X: 33.4 vs 32.0 ms (f32), 10.76 vs 10.07 ms (bf16) — the '
                          'eager step is GPU-bound already (the host enqueues ahead) and the graph executor adds gaps between nodes')
-    ap.add_argument('--serial-steps', type=int, default=3, help='instrumented single-stream steps for the kernels[] table (median)')
-    ap.add_argument('--no-alt-modes', action='store_true',
+    ap.add_argument('--serial-steps', type=int, default=None,
+                    help='instrumented single-stream steps for the kernels[] table (median; default 3)')
+    ap.add_argument('--no-alt-modes', action='store_true', default=None,
                     help='skip timing the other conv-math modes (reported under alt_modes; never part of `value`)')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'], help='process-group backend (nccl = RCCL; gloo only with --dry)')
     ap.add_argument('--dry', action='store_true', help='launch / rendezvous / exchange plumbing only, no GPU work (CPU test of --gpus N)')
-    ap.add_argument('--no-parity', action='store_true', help='skip the cfg2_16x640 parity gate that runs before the timed region')
+    ap.add_argument('--no-parity', action='store_true', default=None,
+                    help='skip the cfg2_16x640 parity gate that runs before the timed region')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step returned (predicted maps, the five losses) as DIR/<name>.npy '
                          '(float32, at most 64 MB: a fixed, seeded sample of the maps when they are larger)')
     args = ap.parse_args()
+    full = args.full or any(v is not None for v in (args.serial_steps, args.no_alt_modes, args.no_parity, args.no_cpu_baseline))
+    if args.serial_steps is None:
+        args.serial_steps = 3
     if args.steps < 1:
         ap.error('--steps must be at least 1')
     if args.dump_outputs and args.dry:
@@ -419,7 +447,7 @@ def main():
 
     # parity gate: the benchmarked configuration vs the reference's golden, on this GPU, in this run, before anything is timed
     parity = None
-    if rank == 0 and not args.no_parity and (args.batch, args.size) == (16, 640):
+    if full and rank == 0 and not args.no_parity and (args.batch, args.size) == (16, 640):
         parity = parity_gate(dev, args.math)
         if not parity['ok']:
             print(json.dumps({'metric': 'train images/sec @640x640 bs=16/GPU', 'value': None, 'parity': parity}), flush=True)
@@ -498,7 +526,7 @@ def main():
     # their buffers
     dumped = dump_outputs(args.dump_outputs, preds, losses) if args.dump_outputs and rank == 0 else None
 
-    # ---- N > 1 diagnostics: exposed part of the exchange, the other exchange form, replica divergence ------------------
+    # ---- N > 1: exposed part of the exchange in the timed region -----------------------------------------------------------
     def exposed_ms(events):
         v = sorted(a.elapsed_time(b) for a, b in events)
         return round(v[len(v) // 2], 4) if v else None
@@ -509,7 +537,59 @@ def main():
         dp_diag.update({'form': form, 'allreduce_exposed_ms': exposed_ms(trainer.exchange_events),
                    'how': 'HIP events on the main stream after the last backward kernel was enqueued and after the exchange was '
                           'joined: the time the step waits for the collective(s); median over the timed steps'})
-        # the other form, same number of steps, same bracket
+
+    # ---- the line: everything here comes from the timed region itself ----------------------------------------------------
+    dtype, math_words, peak_mfma = MATH[args.math]
+    summ = timer.summary(peak_mfma, HBM_ACHIEVABLE_GBS)
+    ms = dt / args.steps * 1e3
+    line = None
+    if rank == 0:
+        value = world * args.batch * args.steps / dt
+        line = {
+            'metric': 'train images/sec @640x640 bs=16/GPU', 'value': round(value, 2), 'unit': 'images/s', 'n_gpus': world,
+            'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms, 3), 'higher_is_better': True, 'scaling': 'weak',
+            'vs_baseline': None, 'dtype': dtype, 'data': 'synthetic',
+            'config': {'workload': 'ResNet18-FPN-DBHead DBNet train step (fwd+DBLoss+bwd+Adam), %dx%d, bs %d/GPU, %s, '
+                                   'random-init weights (BASELINE configs[%d])' % (args.size, args.size, args.batch, math_words,
+                                                                                    1 if args.math in ('f32', 'bf16x3') else 2),
+                       'global_batch': world * args.batch, 'img_size': args.size, 'parallelism': 'dp%d' % world,
+                       'grad_allreduce': (('RCCL sum all-reduce of the flat 49 MB fp32 gradient buffer per step, ' +
+                                           ("ONE call after the backward pass (north_star's single collective)" if not trainer.overlap_allreduce else
+                                            'issued as 4 contiguous buckets under the backward pass (FPN+head, layer4, layer3, rest; '
+                                            '--bucketed-allreduce)'))
+                                          if world > 1 else None)},
+            'timing': {'value_from': 'wall time of the K steps between two barrier+synchronize brackets, max over ranks (driver contract)',
+                       'ms_per_step_median': round(per_step[len(per_step) // 2], 3), 'ms_per_step_min': round(per_step[0], 3),
+                       'ms_per_step_max': round(per_step[-1], 3), 'ms_per_step_in_order': [round(step_ev[i].elapsed_time(step_ev[i + 1]), 2) for i in range(args.steps)],
+                       'host_enqueue_ms_in_order': host_ms,
+                       'instrumented_steps_in_region': timed_steps,
+                       'note': 'per-step figures from HIP events on the main stream at the step boundaries (rank 0); '
+                               '%d of the K steps carry event brackets around their MFMA launches (roofline), which costs those steps ~2 %%' % timed_steps},
+            'engine_clock': clock.result(),
+            'step_launch': ('hipGraph replay of forward + DBLoss + backward (captured after %d eager steps), gradient exchange and Adam '
+                            'launched eagerly; the %d instrumented steps of the region are eager' % (trainer.graph_warmup, timed_steps)
+                            if trainer.use_graph else 'every kernel launched individually (default; --graph replays a captured hipGraph: measured slower)'),
+            'data_parallel': dp_diag,
+            # BASELINE metric, second half ("DB-head GB/s vs HBM peak"), in the timed region
+            'roofline_hbm': hbm_group(summ, args.batch * args.size * args.size, timed_steps),
+            # whole-step rate on the dense convolution count of SURVEY §8d (an EFFECTIVE rate: the structured FPN kernels skip
+            # ~0.77 TFLOP/step of it)
+            'step_tflops': round(TRAIN_GFLOP_PER_IMAGE * (args.size / 640.0)**2 * args.batch / ms, 2),
+            'step_tflop_dense': round(TRAIN_GFLOP_PER_IMAGE * (args.size / 640.0)**2 * args.batch / 1e3, 3),
+            'conv_math': args.math,
+            'final_total_loss': round(final_loss, 5),
+            'full': full,
+        }
+        if dumped is not None:
+            line['dump_outputs'] = dumped
+    if not full:
+        gc.enable()
+        finish(rank, line)
+        return
+
+    # ---- --full: everything below takes steps or runs of its own, after the timed region --------------------------------
+    if world > 1:
+        # the other exchange form, same number of steps, same bracket; then replica divergence
         trainer.overlap_allreduce = not trainer.overlap_allreduce
         trainer.exchange_events = []
         for _ in range(2):
@@ -546,14 +626,12 @@ def main():
     serial_summ = {}
     serial_runs = [t.summary(MATH[args.math][2], HBM_ACHIEVABLE_GBS) for t in serial_timers]
     for k, v in serial_runs[0].items():
-        ms = sorted(r[k]['ms'] for r in serial_runs if k in r)
-        serial_summ[k] = dict(v, ms=ms[len(ms) // 2], ms_min=ms[0], ms_max=ms[-1])
+        runs_ms = sorted(r[k]['ms'] for r in serial_runs if k in r)
+        serial_summ[k] = dict(v, ms=runs_ms[len(runs_ms) // 2], ms_min=runs_ms[0], ms_max=runs_ms[-1])
 
     # dominant kernel = the MFMA kernel (any igemm tile variant or weight-gradient variant) with the largest share of the step
     # when every kernel has the device to itself (under two streams concurrent kernels inflate each other's bracketed
     # durations, which would otherwise decide the ranking); its figures below are the ones measured INSIDE the timed region.
-    dtype, math_words, peak_mfma = MATH[args.math]
-    summ = timer.summary(peak_mfma, HBM_ACHIEVABLE_GBS)
     dname = max((k for k in serial_summ if serial_summ[k]['flops'] > 0 and k in summ), key=lambda k: serial_summ[k]['ms'])
     d = summ[dname]
     achieved = d['flops'] / (d['ms'] * 1e-3) / 1e12
@@ -693,59 +771,21 @@ def main():
         eng.set_conv_math(args.math)
     gc.enable()
     if rank == 0:
-        ms = dt / args.steps * 1e3
-        value = world * args.batch * args.steps / dt
-        line = {
-            'metric': 'train images/sec @640x640 bs=16/GPU', 'value': round(value, 2), 'unit': 'images/s', 'n_gpus': world,
-            'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms, 3), 'higher_is_better': True, 'scaling': 'weak',
-            'vs_baseline': None, 'dtype': dtype, 'data': 'synthetic',
-            'config': {'workload': 'ResNet18-FPN-DBHead DBNet train step (fwd+DBLoss+bwd+Adam), %dx%d, bs %d/GPU, %s, '
-                                   'random-init weights (BASELINE configs[%d])' % (args.size, args.size, args.batch, math_words,
-                                                                                    1 if args.math in ('f32', 'bf16x3') else 2),
-                       'global_batch': world * args.batch, 'img_size': args.size, 'parallelism': 'dp%d' % world,
-                       'grad_allreduce': (('RCCL sum all-reduce of the flat 49 MB fp32 gradient buffer per step, ' +
-                                           ("ONE call after the backward pass (north_star's single collective)" if not trainer.overlap_allreduce else
-                                            'issued as 4 contiguous buckets under the backward pass (FPN+head, layer4, layer3, rest; '
-                                            '--bucketed-allreduce)'))
-                                          if world > 1 else None)},
-            'timing': {'value_from': 'wall time of the K steps between two barrier+synchronize brackets, max over ranks (driver contract)',
-                       'ms_per_step_median': round(per_step[len(per_step) // 2], 3), 'ms_per_step_min': round(per_step[0], 3),
-                       'ms_per_step_max': round(per_step[-1], 3), 'ms_per_step_in_order': [round(step_ev[i].elapsed_time(step_ev[i + 1]), 2) for i in range(args.steps)],
-                       'host_enqueue_ms_in_order': host_ms,
-                       'instrumented_steps_in_region': timed_steps,
-                       'note': 'per-step figures from HIP events on the main stream at the step boundaries (rank 0); '
-                               '%d of the K steps carry event brackets around their MFMA launches (roofline), which costs those steps ~2 %%' % timed_steps},
-            'engine_clock': clock.result(),
-            'step_launch': ('hipGraph replay of forward + DBLoss + backward (captured after %d eager steps), gradient exchange and Adam '
-                            'launched eagerly; the %d instrumented steps of the region are eager' % (trainer.graph_warmup, timed_steps)
-                            if trainer.use_graph else 'every kernel launched individually (default; --graph replays a captured hipGraph: measured slower)'),
-            'data_parallel': dp_diag,
+        line.update({
             'roofline': roofline,
             'roofline_serial': roofline_serial,
-            # BASELINE metric, second half ("DB-head GB/s vs HBM peak"): in the timed region / with the streams serialised
-            'roofline_hbm': hbm_group(summ, args.batch * args.size * args.size, timed_steps),
+            # BASELINE metric, second half ("DB-head GB/s vs HBM peak") with the streams serialised
             'roofline_hbm_serial': hbm_group(serial_summ, args.batch * args.size * args.size, 1),
-            # whole-step rates: on the dense convolution count of SURVEY §8d (an EFFECTIVE rate: the structured FPN kernels
-            # skip ~0.77 TFLOP/step of it) and on the FLOPs the MFMA kernels actually execute (sum over the instrumented step)
-            'step_tflops': round(TRAIN_GFLOP_PER_IMAGE * (args.size / 640.0)**2 * args.batch / ms, 2),
+            # whole-step rate on the FLOPs the MFMA kernels actually execute (sum over the instrumented step)
             'step_tflops_executed': round(sum(v['flops'] for v in serial_summ.values()) / 1e9 / ms, 2),
-            'step_tflop_dense': round(TRAIN_GFLOP_PER_IMAGE * (args.size / 640.0)**2 * args.batch / 1e3, 3),
             'step_tflop_executed': round(sum(v['flops'] for v in serial_summ.values()) / 1e12, 3),
             'kernels': kernels,
-            'conv_math': args.math,
             'alt_modes': alt,
-            'final_total_loss': round(final_loss, 5),
             'parity': parity,
-        }
-        if dumped is not None:
-            line['dump_outputs'] = dumped
+        })
         if not args.no_cpu_baseline and world == 1:  # reported at N=1 only
             line['cpu_baseline'] = cpu_baseline()
-        print(json.dumps(line), flush=True)
-    if dist.is_initialized():
-        dist.barrier()
-        dist.destroy_process_group()
-
+    finish(rank, line)
 
 if __name__ == '__main__':
     main()

@@ -1,4 +1,4 @@
-"""Print the interesting parts of a bench.py JSON line (file argument): value, per-step median, clock, roofline, kernels[]."""
+"""Print the interesting parts of a `bench.py --full` JSON line (file argument): value, per-step median, clock, roofline, kernels[]."""
 import json
 import sys
 

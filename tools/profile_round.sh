@@ -19,7 +19,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-A="--no-cpu-baseline --no-alt-modes --no-parity"   # (the profiled passes skip the parity gate: its extra step would sit in the traces; the plain bench line below runs it)
+A="--full --no-cpu-baseline --no-alt-modes --no-parity"   # (the profiled passes skip the parity gate: its extra step would sit in the traces; the un-profiled full line below runs it)
 rocprofv3 --kernel-trace -d $O/trace -o r01 -- python3 $R/bench.py --steps 10 --warmup 3 $A > $O/bench_under_rocprof.log 2>&1
 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o r01 -- python3 $R/bench.py --steps 2 --warmup 1 $A > $O/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write -o r01 -- python3 $R/bench.py --steps 2 --warmup 1 $A > $O/pmc_write.log 2>&1
@@ -30,7 +30,7 @@ python3 tools/step_breakdown.py $O/trace/r01_results.db $K32 > $O/step_breakdown
 python3 tools/pmc_traffic.py $O/pmc_fetch/r01_results.db $O/pmc_write/r01_results.db $O/pmc_traffic.json > /dev/null
 grep '^{"metric"' $O/bench_under_rocprof.log > $O/bench_under_rocprof.json
 cp $O/pmc_traffic.json profiles/${TAG}_pmc_traffic.json   # bench.py reads the per-kernel traffic of the newest round from profiles/
-python3 bench.py --steps 20 --warmup 5 > $O/bench_n1.log 2>&1
+python3 bench.py --steps 20 --warmup 5 --full > $O/bench_n1.log 2>&1
 grep '^{"metric"' $O/bench_n1.log > $O/bench_n1.json
 cd /tmp
 rocprofv3 --kernel-trace -d $O/trace_bf16 -o r01 -- python3 $R/bench.py --steps 10 --warmup 3 $A --math bf16 > $O/bench_bf16_under_rocprof.log 2>&1
@@ -79,7 +79,7 @@ cp $O/pmc_traffic_bf16.json profiles/${TAG}_pmc_traffic_bf16.json
 cp $O/pmc_traffic_fp16.json profiles/${TAG}_pmc_traffic_fp16.json
 # (the plain lines of the alternative modes come AFTER the mode's traffic file exists: bench.py quotes it in roofline.traffic)
 for m in bf16 bf16x3; do   # the plain (un-profiled) lines of the two alternative modes, each with its own roofline and parity object
-  python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-alt-modes --math $m 2>/dev/null | grep '^{"metric"' > $O/bench_n1_$m.json
+  python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-alt-modes --math $m 2>/dev/null | grep '^{"metric"' > $O/bench_n1_$m.json
 done
 python3 tools/pmc_mfma_busy.py $O/pmc_mfma/r01_results.db > $O/mfma_busy_f32.txt 2>&1
 python3 tools/pmc_mfma_busy.py $O/pmc_mfma16/r01_results.db > $O/mfma_busy_bf16.txt 2>&1
