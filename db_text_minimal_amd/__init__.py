@@ -5,3 +5,5 @@ from .models import DBTextModel  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
 from .train import DBTrainer  # noqa: F401
 from .gt_maps import gt_collate, make_gt_maps, normalize_images, offset_polygon  # noqa: F401
+from .postprocess import SegDetectorRepresenter, detect_boxes, detect_polygons  # noqa: F401
+from .det_eval import DetectionDetEvalEvaluator, DetectionIoUEvaluator, QuadMetric, polygon_overlaps  # noqa: F401

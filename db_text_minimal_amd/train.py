@@ -422,15 +422,72 @@ def _collective_device(model):
     return torch.device('cpu')
 
 
-def evaluate(model, criterion, loader, thresh=0.3, device=None, pixel_metric=True):
+DETECTION_DEFAULTS = dict(thresh=0.25, box_thresh=0.50, unclip_ratio=1.5, is_output_polygon=True, protocol='iou', max_candidates=1000)
+
+
+def detection_config(detection):
+    """`detection` of evaluate / fit: True for the reference's `metric:` section (example_config.yaml), or a dict overriding
+    some of DETECTION_DEFAULTS (protocol 'iou' or 'deteval')"""
+    cfg = dict(DETECTION_DEFAULTS)
+    if detection is not True:
+        unknown = set(detection) - set(cfg)
+        if unknown:
+            raise ValueError('unknown detection settings: %s' % sorted(unknown))
+        cfg.update(detection)
+    if cfg['protocol'] not in ('iou', 'deteval'):
+        raise ValueError("detection protocol must be 'iou' or 'deteval'")
+    return cfg
+
+
+def _detection_scores(raws, evaluator, group, device):
+    """gather_measure over every rank's images: the counts (gtCare, detCare, the matched count or the two accums, images) are
+    SUMMED over the ranks in one all-reduce, so every rank gets the single-process result and takes the same decisions"""
+    from .det_eval import DetectionDetEvalEvaluator, gather_counts
+    deteval = isinstance(evaluator, DetectionDetEvalEvaluator)
+    c = [0, 0, 0, 0, 0]
+    for r in raws:
+        c[0] += r['gtCare']
+        c[1] += r['detCare']
+        c[2] += r['recallAccum'] if deteval else r['detMatched']
+        c[3] += r['precisionAccum'] if deteval else r['detMatched']
+        c[4] += 1
+    if dist.is_available() and dist.is_initialized():
+        t = torch.tensor([float(v) for v in c], dtype=torch.float64, device=device)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        c = t.tolist()
+        if not deteval:
+            c = [int(round(v)) for v in c]
+    gc, dc, rs, ps, n = c
+    R = 0 if gc == 0 else float(rs) / gc
+    P = 0 if dc == 0 else float(ps) / dc
+    H = 0 if R + P == 0 else 2 * R * P / (R + P)
+    m = gather_counts({'precision': P, 'recall': R, 'hmean': H}, int(n))
+    return {'precision': m['precision'].avg, 'recall': m['recall'].avg, 'hmean': m['fmeasure'].avg}
+
+
+def evaluate(model, criterion, loader, thresh=0.3, device=None, pixel_metric=True, detection=None, process_group=None):
     """train.py:228-262: eval-mode forward under no_grad, DBLoss on the 2-channel output (single value), the pixel metric
-    on device.  Returns (mean test loss as a float, score dict of the RunningScore over the whole loader)."""
+    on device.  Returns (mean test loss as a float, score dict of the RunningScore over the whole loader).
+
+    detection (None: off): True or a dict over DETECTION_DEFAULTS — train.py:276-286: every batch runs SegDetectorRepresenter
+    (polygons or boxes) and QuadMetric.validate_measure on batch['anns'] / batch['ignore_tags'], every image scored; the score
+    dict gains precision / recall / hmean (gather_measure's recall.avg, precision.avg, fmeasure.avg).  Under data parallel the
+    counts are summed over the ranks of `process_group` (the result of one process scoring the whole set)."""
     was_training = model.training
     model.eval()
     running = None
     if pixel_metric:
         from .text_metrics import RunningScore
         running = RunningScore(2)
+    seg = metric = None
+    raws = []
+    if detection is not None:
+        from .det_eval import DetectionDetEvalEvaluator, DetectionIoUEvaluator, QuadMetric
+        from .postprocess import SegDetectorRepresenter
+        cfg = detection_config(detection)
+        seg = SegDetectorRepresenter(thresh=cfg['thresh'], box_thresh=cfg['box_thresh'], max_candidates=cfg['max_candidates'],
+                                     unclip_ratio=cfg['unclip_ratio'])
+        metric = QuadMetric(DetectionIoUEvaluator() if cfg['protocol'] == 'iou' else DetectionDetEvalEvaluator())
     total, n = None, 0
     with torch.no_grad():
         for batch in loader:
@@ -443,25 +500,38 @@ def evaluate(model, criterion, loader, thresh=0.3, device=None, pixel_metric=Tru
             n += 1
             if running is not None:
                 running.update_device(preds[:, 0, :, :], batch['prob_map'], batch['supervision_mask'], thresh)  # no host sync
+            if seg is not None:
+                shape = {'shape': [(preds.shape[2], preds.shape[3])] * preds.shape[0]}
+                out = seg.polygons(shape, preds) if cfg['is_output_polygon'] else seg(shape, preds)
+                raws.extend(metric.validate_measure(batch, out))
     model.train(was_training)
     score = running.get_scores()[0] if (n and running is not None) else {}
+    if seg is not None:
+        ctl = _collective_device(model) if (dist.is_available() and dist.is_initialized()) else None
+        score = dict(score, **_detection_scores(raws, metric.evaluator, process_group, ctl))
     return (float(total) / max(n, 1) if total is not None else float('nan')), score
 
 
 def fit(model, criterion, optimizer, train_loader, test_loader=None, epochs=1, scheduler=None, lrs_mode=None, thresh=0.3,
-        best_cp_path=None, last_cp_path=None, device=None, log=None, process_group=None, trainer=None, pixel_metric=True):
+        best_cp_path=None, last_cp_path=None, device=None, log=None, process_group=None, trainer=None, pixel_metric=True,
+        detection=None, best_hmean_cp_path=None):
     """The reference's training driver (train.py:146-318): per epoch a pass over `train_loader` through DBTrainer.step
     (lr scheduler stepped per iteration when lrs_mode == 'poly', train.py:172-173), the running pixel metric
     (train.py:175-181, on device), then evaluate() on `test_loader`, the reference's best-checkpoint rule
     (`test_loss <= best_test_loss and train_loss <= best_train_loss`, train.py:301-305; `train_loss` is the epoch SUM as
     there), ReduceLROnPlateau-style schedulers stepped with the test loss when lrs_mode == 'reduce' (train.py:307-308), and
-    the final state_dict at `last_cp_path` (train.py:316).  Box-level P/R/HMean (train.py:277-299) needs the host OpenCV
-    post-processing and is left to the caller.  Returns a list of per-epoch dicts.
+    the final state_dict at `last_cp_path` (train.py:316).  Box-level P/R/HMean (train.py:277-299) is opt-in through
+    `detection` (below).  Returns a list of per-epoch dicts.
 
     Data parallel: each rank iterates its own shard of the loaders.  The epoch's train-loss sum and the test loss are
     AVERAGED OVER THE RANKS before they are compared, recorded or given to the scheduler, so every rank takes the same
     save / no-save decision (the checkpoint barrier is reached by all or none) and the same learning-rate schedule.
-    `trainer`: a ready DBTrainer (default: built here); `pixel_metric=False` skips the device pixel metric."""
+    `trainer`: a ready DBTrainer (default: built here); `pixel_metric=False` skips the device pixel metric.
+
+    detection (None: off, and every record, return value and timing is as without it): True or a dict over
+    DETECTION_DEFAULTS — evaluate() also scores the test set's detections (train.py:276-299): each epoch record gains
+    test_precision / test_recall / test_hmean, and `hmean >= best_hmean` (from 0) saves `best_hmean_cp_path`.  The counts
+    behind them are summed over the ranks, so the save decision is rank-uniform."""
     own_trainer = trainer is None
     if own_trainer:
         # (the heap freeze of DBTrainer.freeze_heap is taken for the duration of this call and undone on return)
@@ -484,6 +554,7 @@ def fit(model, criterion, optimizer, train_loader, test_loader=None, epochs=1, s
             dist.barrier(group=process_group)
 
     best_test, best_train = float('inf'), float('inf')
+    best_hmean = 0
     history = []
     steps = 0
     for epoch in range(epochs):
@@ -504,7 +575,11 @@ def fit(model, criterion, optimizer, train_loader, test_loader=None, epochs=1, s
         train_loss = float(train_sum) if train_sum is not None else float('nan')
         test_loss, test_score = float('nan'), {}
         if test_loader is not None:
-            test_loss, test_score = evaluate(model, criterion, test_loader, thresh=thresh, device=device, pixel_metric=pixel_metric)
+            if detection is None:
+                test_loss, test_score = evaluate(model, criterion, test_loader, thresh=thresh, device=device, pixel_metric=pixel_metric)
+            else:
+                test_loss, test_score = evaluate(model, criterion, test_loader, thresh=thresh, device=device, pixel_metric=pixel_metric,
+                                                 detection=detection, process_group=process_group)
         local = (train_loss, test_loss)
         train_loss, test_loss = _mean_over_ranks(local, process_group, ctl_dev)  # rank-uniform from here on
         rec = {'epoch': epoch + 1, 'global_steps': steps, 'lr': optimizer.param_groups[0]['lr'], 'train_loss_sum': train_loss,
@@ -518,6 +593,14 @@ def fit(model, criterion, optimizer, train_loader, test_loader=None, epochs=1, s
                 if best_cp_path:
                     save(best_cp_path)
                 rec['saved_best'] = True
+            if detection is not None:
+                hmean = test_score['hmean']  # rank-uniform: evaluate() summed the counts over the ranks
+                rec.update(test_precision=test_score['precision'], test_recall=test_score['recall'], test_hmean=hmean)
+                if hmean >= best_hmean:
+                    best_hmean = hmean
+                    if best_hmean_cp_path:
+                        save(best_hmean_cp_path)
+                    rec['saved_best_hmean'] = True
             if lrs_mode == 'reduce' and scheduler is not None:
                 scheduler.step(test_loss)
         if log is not None:

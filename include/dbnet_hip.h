@@ -470,6 +470,32 @@ int dbn_detect_poly_host(const void* recs, const int* counts, const int* nv, con
                          int H, int W, const double* params, const int* dest_hw, int* poly_n, int* poly_off, int* poly_xy, int poly_cap,
                          int* poly_total, double* scores, double* info, int* approx_xy);
 
+/* ---- Text-detection scoring (csrc/det_eval.hip): the overlap matrices of the reference's evaluators
+ *      (src/iou.py, src/deteval.py) and their matching protocols.  Polygons are oriented so that their shoelace signed area is
+ *      >= 0; area = |signed area|; overlap(A, B) = the integral of w_A * w_B (winding numbers), exactly area(A n B) for simple
+ *      polygons, a winding-weighted overlap for non-simple ones (flagged).  Exact predicates with symbolic perturbation. ---- */
+/* bytes of the dbn_det_eval_overlaps workspace (48 per polygon) */
+long dbn_det_eval_ws_bytes(int n_polys);
+/* verts: (x, y) fp64 pairs of every polygon of the batch, packed; poff [n_polys + 1] int: polygon k is verts[poff[k] ..
+ * poff[k + 1]), at least 3 vertices; img [N][5] int64 = {first GT polygon, G, first detection polygon, D, pair offset} with
+ * pair offset = sum over earlier images of G * D; n_pairs = the sum over all images.  Outputs: inter [n_pairs] fp64, per image the
+ * row-major G x D overlap matrix at its pair offset; area [n_polys] fp64; nonsimple [n_polys] int (1: two non-adjacent edges
+ * touch or cross, two adjacent edges overlap collinearly, or fewer than 3 non-zero edges).  cull = 0 computes pairs with
+ * disjoint bounding boxes too (measurement only; the product culls).  ws: dbn_det_eval_ws_bytes, any contents. */
+int dbn_det_eval_overlaps(const double* verts, const int* poff, int n_polys, const long long* img, int N, long n_pairs, int cull, void* ws,
+                          double* inter, double* area, int* nonsimple, void* stream);
+/* host: per image what the reference's evaluate_image computes from the overlaps (host memory).  protocol 0: iou.py
+ * (params {iou_constraint, area_precision_constraint}), 1: deteval.py (params {area_recall_constraint,
+ * area_precision_constraint, ev_param_ind_center_diff_thr, mtype_oo_o, mtype_om_o, mtype_om_m}).  sizes [N][2] = (G, D);
+ * inter as dbn_det_eval_overlaps writes it; gt_area / gt_ignore / gt_cd packed over the images' GT polygons, det_area / det_cd
+ * over the detections; *_cd [.][3] = vertex mean x, y and bounding-box diagonal as deteval.py computes them (protocol 1 only).
+ * Outputs: stats [N][8] = {precision, recall, hmean, gtCare, detCare, detMatched, recallAccum, precisionAccum}; det_dc [D]
+ * (1: don't care); rows: per image from 2 * sum over earlier images of (G + D), n_rows[n] records {pair, kind, gt, det}
+ * (kind 0: one-to-one, 1: one-to-many (gt, its dets; det -1 for an empty list), 2: many-to-one (gts -1 likewise)). */
+int dbn_det_eval_match_host(int protocol, int N, const int* sizes, const double* inter, const double* gt_area, const double* det_area,
+                            const unsigned char* gt_ignore, const double* gt_cd, const double* det_cd, const double* params, double* stats,
+                            unsigned char* det_dc, int* rows, int* n_rows);
+
 
 /* =====================================================================================================================
  * Activation storage types (BASELINE configs[2]-[4]).  Every entry point above that moves activation tensors has a `_t`
