@@ -7,3 +7,4 @@ from .train import DBTrainer  # noqa: F401
 from .gt_maps import gt_collate, make_gt_maps, normalize_images, offset_polygon  # noqa: F401
 from .postprocess import SegDetectorRepresenter, detect_boxes, detect_polygons  # noqa: F401
 from .det_eval import DetectionDetEvalEvaluator, DetectionIoUEvaluator, QuadMetric, polygon_overlaps  # noqa: F401
+from .augment import DeviceBatches, augment_images, image_collate, plan_augment, plan_letterbox, preprocess_image  # noqa: F401

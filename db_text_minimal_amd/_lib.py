@@ -40,6 +40,9 @@ SIGNATURES = {
     'dbn_detect': 'piiiifi' + 'ppppp',
     'dbn_detect_host': 'pp' + 'iiii' + 'ppppp',
     'dbn_poly_offset_paths': 'pippipp',
+    'dbn_warp_affine_u8': 'plppiiiplp',
+    'dbn_resize_cubic_u8': 'plppiiiplp',
+    'dbn_resize_linear_norm_u8': 'plppiii' + 'fff' + 'pp',
     'dbn_detect_poly_ws_bytes': 'iiii',
     'dbn_detect_poly_verts_cap': 'iii',
     'dbn_detect_poly': 'piiiifi' + 'pppppp',

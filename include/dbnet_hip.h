@@ -420,6 +420,27 @@ int dbn_poly_offset(const double* xy, int n, const double* delta, int* out_xy, i
  * the offset vanishes).  dbn_poly_offset's own result is unchanged by it. */
 int dbn_poly_offset_paths(const double* xy, int n, const double* delta, int* out_xy, int cap, int* out_n, int* out_paths);
 
+/* ---- the loader's geometric stage on the device: flip + rotate, cubic resize of a crop window, letterbox + normalise
+ *      (csrc/resample.hip, db_text_minimal_amd/augment.py).  PARITY UNPINNED against cv2 / imgaug. ---- */
+/* uint8 HWC images, 3 channels, packed: image n is described by desc[n][12] int64 — 0 byte offset of its source in src,
+ * 1/2 source height / width, 3 offset of its output in dst (bytes; elements of out for the linear stage, which needs 0),
+ * 4/5 height / width of the whole resized image (the source size for the warp), 6/7 row / column of the window's origin in
+ * it, 8/9 window height / width (what is computed and stored, row-major, at dst + 3); 10 flip (warp only), 11 unused — and
+ * coef[n][6] fp64: the inverse affine map (warp), or scale_x, scale_y = 1 / ((double)dst / src) as cv2.resize computes
+ * them.  A descriptor whose regions leave src_bytes / dst_bytes, or whose window leaves the resized image, is skipped.
+ * max_h / max_w bound the windows (the grid).  All sizes <= 65535. */
+/* cv2.warpAffine(INTER_LINEAR, BORDER_CONSTANT 0) of the image (flipped left-right first if flip), output the size of
+ * the input (window = the whole image). */
+int dbn_warp_affine_u8(const unsigned char* src, long src_bytes, const long long* desc, const double* coef, int N, int max_h, int max_w,
+                       unsigned char* dst, long dst_bytes, void* stream);
+/* cv2.resize(INTER_CUBIC) of the image to desc 4 x 5, only the window 6-9. */
+int dbn_resize_cubic_u8(const unsigned char* src, long src_bytes, const long long* desc, const double* coef, int N, int max_h, int max_w,
+                        unsigned char* dst, long dst_bytes, void* stream);
+/* cv2.resize(INTER_LINEAR) of the image to desc 4 x 5 (window 0, 0, desc 4, desc 5), written normalised into the top-left
+ * corner of out[n][3][CH][CW] = (float)u8 - m_c, and -m_c over the rest of the canvas: every element written once. */
+int dbn_resize_linear_norm_u8(const unsigned char* src, long src_bytes, const long long* desc, const double* coef, int N, int CH, int CW,
+                              float m0, float m1, float m2, float* out, void* stream);
+
 /* ---- text boxes from probability maps: boxes_from_bitmap of postprocess.py:105-141 (csrc/detect.hip,
  *      db_text_minimal_amd/postprocess.py detect_boxes).  PARITY UNPINNED against cv2 / pyclipper. ---- */
 /* One record per candidate (72 bytes):
