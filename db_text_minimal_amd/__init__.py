@@ -8,3 +8,4 @@ from .gt_maps import gt_collate, make_gt_maps, normalize_images, offset_polygon 
 from .postprocess import SegDetectorRepresenter, detect_boxes, detect_polygons  # noqa: F401
 from .det_eval import DetectionDetEvalEvaluator, DetectionIoUEvaluator, QuadMetric, polygon_overlaps  # noqa: F401
 from .augment import DeviceBatches, augment_images, image_collate, plan_augment, plan_letterbox, preprocess_image  # noqa: F401
+from .word_crops import crop_words, perspective_maps  # noqa: F401

@@ -43,6 +43,8 @@ SIGNATURES = {
     'dbn_warp_affine_u8': 'plppiiiplp',
     'dbn_resize_cubic_u8': 'plppiiiplp',
     'dbn_resize_linear_norm_u8': 'plppiii' + 'fff' + 'pp',
+    'dbn_perspective_maps': 'piiipp',
+    'dbn_warp_perspective_u8': 'plppiiiplp',
     'dbn_detect_poly_ws_bytes': 'iiii',
     'dbn_detect_poly_verts_cap': 'iii',
     'dbn_detect_poly': 'piiiifi' + 'pppppp',

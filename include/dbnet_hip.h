@@ -441,6 +441,19 @@ int dbn_resize_cubic_u8(const unsigned char* src, long src_bytes, const long lon
 int dbn_resize_linear_norm_u8(const unsigned char* src, long src_bytes, const long long* desc, const double* coef, int N, int CH, int CW,
                               float m0, float m1, float m2, float* out, void* stream);
 
+/* ---- word crops of detected boxes: test_ocr.py:160-177 (cv2.getPerspectiveTransform + cv2.warpPerspective per box;
+ *      csrc/resample.hip, db_text_minimal_amd/word_crops.py).  PARITY UNPINNED against cv2. ---- */
+/* host: for K quads quads[K][4][2] (fp32 (x, y), the corners mapped to (0, 0), (out_w, 0), (out_w, out_h), (0, out_h)),
+ * fwd[K][9] = getPerspectiveTransform (fp64, row-major; a singular system gives zeros with fwd[8] = 1) and inv[K][9] = its
+ * inverse as warpPerspective computes it (invert, DECOMP_LU: the zero matrix when the determinant is 0). */
+int dbn_perspective_maps(const float* quads, int K, int out_h, int out_w, double* fwd, double* inv);
+/* cv2.warpPerspective(INTER_LINEAR, BORDER_CONSTANT 0) of K crops into dst[K][out_h][out_w][3] uint8 (every byte
+ * written; dst_bytes >= K * out_h * out_w * 3): crop k samples the uint8 HWC image desc[k][3] int64 = {byte offset in
+ * src, height, width} through inv[k][9] (fp64, dbn_perspective_maps).  A descriptor that leaves src_bytes or whose sides
+ * leave 1 .. 65535 gives a zero crop.  K > 0, sides <= 65535. */
+int dbn_warp_perspective_u8(const unsigned char* src, long src_bytes, const long long* desc, const double* inv, int K, int out_h, int out_w,
+                            unsigned char* dst, long dst_bytes, void* stream);
+
 /* ---- text boxes from probability maps: boxes_from_bitmap of postprocess.py:105-141 (csrc/detect.hip,
  *      db_text_minimal_amd/postprocess.py detect_boxes).  PARITY UNPINNED against cv2 / pyclipper. ---- */
 /* One record per candidate (72 bytes):
