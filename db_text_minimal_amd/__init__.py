@@ -9,3 +9,4 @@ from .postprocess import SegDetectorRepresenter, detect_boxes, detect_polygons  
 from .det_eval import DetectionDetEvalEvaluator, DetectionIoUEvaluator, QuadMetric, polygon_overlaps  # noqa: F401
 from .augment import DeviceBatches, augment_images, image_collate, plan_augment, plan_letterbox, preprocess_image  # noqa: F401
 from .word_crops import crop_words, perspective_maps  # noqa: F401
+from .render import draw_outlines, image_views, minmax_scale_u8, overlay_heatmap, render_detections  # noqa: F401

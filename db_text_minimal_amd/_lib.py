@@ -45,6 +45,10 @@ SIGNATURES = {
     'dbn_resize_linear_norm_u8': 'plppiii' + 'fff' + 'pp',
     'dbn_perspective_maps': 'piiipp',
     'dbn_warp_perspective_u8': 'plppiiiplp',
+    'dbn_draw_strokes': 'pplpipliiiip',
+    'dbn_render_minmax': 'ppilplliifpp',
+    'dbn_render_paint': 'ppppilplliifppfp',
+    'dbn_minmax_scale_u8': 'piiippp',
     'dbn_detect_poly_ws_bytes': 'iiii',
     'dbn_detect_poly_verts_cap': 'iii',
     'dbn_detect_poly': 'piiiifi' + 'pppppp',

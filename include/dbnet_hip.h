@@ -454,6 +454,34 @@ int dbn_perspective_maps(const float* quads, int K, int out_h, int out_w, double
 int dbn_warp_perspective_u8(const unsigned char* src, long src_bytes, const long long* desc, const double* inv, int K, int out_h, int out_w,
                             unsigned char* dst, long dst_bytes, void* stream);
 
+/* ---- showing a detection result: utils.draw_bbox + the heat-map overlay of utils.visualize_polygon / visualize_heatmap
+ *      (utils.py:110-113,202-283; csrc/render.hip, db_text_minimal_amd/render.py).  Thick strokes are this project's
+ *      definition, the resize is PARITY UNPINNED against cv2. ---- */
+/* cv2.polylines(isClosed) of E edges, one colour: dst = src (bytes bytes of packed uint8 HWC images; src may be dst, then
+ * nothing is copied), then every pixel of image edges[e][0] within thickness / 2 of the closed segment edges[e][1..4] =
+ * (xa, ya, xb, yb) is set to (c0, c1, c2); thickness 1 paints the 8-connected line of fillPoly's border instead.
+ * desc[n][3] int64 = {byte offset of image n, height, width}.  Vertices within +-2^20, 1 <= thickness <= 255; an edge
+ * whose image, descriptor or vertices break this is skipped.  E may be 0. */
+int dbn_draw_strokes(const unsigned char* src, unsigned char* dst, long bytes, const long long* desc, int N, const int* edges, long E,
+                     int thickness, int c0, int c1, int c2, void* stream);
+/* The heat map.  desc[n][5] int64 = {first pixel of image n in the packed run of n_px pixels, height, width, valid map
+ * rows, valid map columns}; coef[n][4] fp64 = {scale_x, scale_y (1 / ((double)dst / src), as cv2.resize), vmin, vmax}.
+ * Image n's map is prob + n * img_stride, rows row_stride floats apart, map_elems floats in all.  binary != 0: a tap
+ * reads 1 where the map is > thresh, else 0.
+ * dbn_render_minmax: mm[n] (8 bytes per image) = ordered keys of the minimum and maximum of the map resized to image n
+ * (float INTER_LINEAR); the resized values are not stored. */
+int dbn_render_minmax(const long long* desc, const double* coef, int N, long n_px, const float* prob, long map_elems, long img_stride,
+                      int row_stride, int binary, float thresh, void* mm, void* stream);
+/* dst pixel = rint(src pixel * (1 - alpha) + lut[index] * alpha), index = matplotlib's Normalize + Colormap index of the
+ * resized map value with the limits of mm (dbn_render_minmax) or, mm NULL, of coef.  lut: 256 x (r | g << 8 | b << 16).
+ * Every byte of dst is written once; src may be dst; 0 <= alpha <= 1. */
+int dbn_render_paint(const unsigned char* src, unsigned char* dst, const long long* desc, const double* coef, int N, long n_px, const float* prob,
+                     long map_elems, long img_stride, int row_stride, int binary, float thresh, const void* mm, const void* lut, float alpha,
+                     void* stream);
+/* utils.minmax_scaler_img: x [N][3][H][W] fp32 -> out [N][H][W][3] = (uint8)((x - min) * (1 / (max - min) * 255)) in
+ * float32 per image, truncated; a constant image gives zeros.  mm: 8 bytes per image of workspace. */
+int dbn_minmax_scale_u8(const float* x, int N, int H, int W, void* mm, unsigned char* out, void* stream);
+
 /* ---- text boxes from probability maps: boxes_from_bitmap of postprocess.py:105-141 (csrc/detect.hip,
  *      db_text_minimal_amd/postprocess.py detect_boxes).  PARITY UNPINNED against cv2 / pyclipper. ---- */
 /* One record per candidate (72 bytes):
