@@ -1,0 +1,220 @@
+"""Reading word crops on the device: everything around the text recogniser of the reference's full pipeline
+(test_ocr.py:59-108,179-200, test_webcam.py), batched.  The recogniser itself (clova_ocr's Model) stays the user's nn.Module.
+
+  words_to_input(crops, rgb, bgr, dtype)       rec_preprocess of every crop in one launch: uint8 [K, h, w, 3] ->
+                                               [K, 1 | 3, h, w] in fp32 / fp16 / bf16
+  greedy_decode(logits, mode, lengths)         predict()'s argmax, softmax, maximum probability, cumprod and the CTC /
+                                               attention collapse: (codes, count, score) on the device, two launches
+  CTCLabelConverter / AttnLabelConverter       codes -> strings, from one device-to-host copy
+  recognize_words(images, boxes, model, ...)   crop_words -> words_to_input -> model -> greedy_decode -> strings
+
+Pinned: the grey formula against PIL's convert('L') and the normalisation against torch's ToTensor arithmetic (on the
+CPU, tests/test_recognise_cpu.py); the decode against a numpy restatement that equals the reference's torch ops.
+UNPINNED: clova_ocr's own preprocessing and converters, which are not in the reference tree.
+"""
+import numpy as np
+import torch
+
+from ._lib import check, lib
+from .augment import _stream
+from .word_crops import SIZE, crop_words
+
+_INT_MAX = 2 ** 31 - 1
+_AT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # DBN_AT_* of include/dbnet_hip.h
+BLANK, EOS = 0, 1  # '[blank]' of the CTC table, '[s]' of the attention table
+_MODES = {'ctc': 0, 'attn': 1}
+
+
+def input_table():
+    """fp32 [256]: ToTensor then sub_(0.5).div_(0.5) of every byte, (g / 255 - 0.5) / 0.5 in float32, in that order"""
+    g = np.arange(256, dtype=np.float32)
+    return (g / np.float32(255) - np.float32(0.5)) / np.float32(0.5)
+
+
+_tables = {}
+
+
+def _table_on(dev):
+    if dev not in _tables:
+        _tables[dev] = torch.from_numpy(input_table()).to(dev)
+    return _tables[dev]
+
+
+def words_to_input(crops, rgb=False, bgr=False, dtype=torch.float32):
+    """uint8 device crops [K, h, w, 3] (crop_words) -> the recogniser's input [K, 1, h, w] (grey) or [K, 3, h, w] (rgb=True,
+    planar, the crops' channel order), in `dtype` (float32, float16 or bfloat16), one launch on the current stream.
+
+    Grey is PIL's convert('L') in integers, (19595 c0 + 38470 c1 + 7471 c2 + 32768) >> 16 with c0 .. c2 in the crops'
+    channel order (RGB crops when the images were RGB); bgr=True swaps the weights for BGR crops.  The value is
+    (g / 255 - 0.5) / 0.5 from a 256-entry float32 table (input_table), so float32 output is that arithmetic bit for bit and
+    the 16-bit types are its round-to-nearest-even conversions."""
+    if not isinstance(crops, torch.Tensor) or crops.dtype != torch.uint8 or crops.dim() != 4 or crops.shape[3] != 3:
+        raise ValueError('crops must be a uint8 [K, h, w, 3] tensor')
+    if not crops.is_cuda:
+        raise ValueError('words_to_input runs on a GPU device, not %s' % crops.device)
+    if dtype not in _AT:
+        raise ValueError('dtype must be float32, float16 or bfloat16, got %r' % (dtype, ))
+    K, h, w, _ = crops.shape
+    if h < 1 or w < 1:
+        raise ValueError('crop size %d x %d' % (h, w))
+    n_px = K * h * w
+    if -(-n_px // 1024) > _INT_MAX:  # dbn_words_to_input's grid: four pixels per thread, 256 threads
+        raise ValueError('%d crops of %d x %d are too many for one call' % (K, h, w))
+    out = torch.empty((K, 3 if rgb else 1, h, w), device=crops.device, dtype=dtype)
+    if K == 0:
+        return out
+    crops = crops.contiguous()
+    check(lib().dbn_words_to_input(_AT[dtype], crops.data_ptr(), n_px, h * w, int(bool(rgb)), int(bool(bgr)), _table_on(crops.device).data_ptr(),
+                                   out.data_ptr(), _stream(crops.device)), 'words_to_input')
+    return out
+
+
+def greedy_decode(logits, mode='ctc', lengths=None):
+    """Greedy decode of a recogniser's output logits [B, T, C] (float32, float16 or bfloat16 on the device; widened to
+    float32 exactly) -> (codes int32 [B, T], count int32 [B], score float32 [B]), device tensors.  Two launches on the current
+    stream, no host synchronisation.  lengths: optional int32 [B], the steps of each sequence (clamped to 0 .. T; default T).
+
+    Per step t < len_b: m = max_c x, k_t = the smallest index with x == m (exact), p_t = 1 / sum_c exp(x_c - m) accumulated in
+    float32.  A row that contains a NaN gives k_t = the index of its first NaN and p_t = NaN, which is torch.max on the CPU.
+      mode 'ctc'   step t is kept iff k_t != 0 ([blank]) and (t == 0 or k_t != k_{t-1}); score = the product of p_t over ALL
+                   len_b steps (the reference's cumprod covers every step, not only the kept ones).
+      mode 'attn'  e = the first t with k_t == 1 ([s]), or len_b if there is none; the steps t < e are kept and score = the
+                   product of their p_t; the empty product is 1.0.
+    The product is formed in float32 in ascending t, so two runs agree bit for bit.  codes holds the kept k_t packed to the
+    left and -1 after them; every element of all three outputs is written.
+
+    Two quirks of the reference's predict() are deliberately not reproduced: str.find returning -1 drops the last character
+    when no '[s]' occurs, and cumprod(...)[-1] raises on an empty prefix ('[s]' first)."""
+    if mode not in _MODES:
+        raise ValueError("mode must be 'ctc' or 'attn', got %r" % (mode, ))
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 3 or logits.dtype not in _AT:
+        raise ValueError('logits must be a float32, float16 or bfloat16 [B, T, C] tensor')
+    if not logits.is_cuda:
+        raise ValueError('greedy_decode runs on a GPU device, not %s' % logits.device)
+    B, T, C = logits.shape
+    if C < 1:
+        raise ValueError('logits need at least one class')
+    if C > _INT_MAX or B * T > _INT_MAX:
+        raise ValueError('logits [%d, %d, %d] are too large for one call' % (B, T, C))
+    dev = logits.device
+    codes = torch.empty((B, T), device=dev, dtype=torch.int32)
+    count = torch.empty((B, ), device=dev, dtype=torch.int32)
+    score = torch.empty((B, ), device=dev, dtype=torch.float32)
+    len_ptr = None
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).contiguous()
+        if lengths.shape != (B, ):
+            raise ValueError('lengths must have shape [%d], got %s' % (B, tuple(lengths.shape)))
+        len_ptr = lengths.data_ptr()
+    if B == 0:
+        return codes, count, score
+    if T == 0:
+        return codes, count.zero_(), score.fill_(1.0)
+    logits = logits.contiguous()
+    ws = torch.empty((lib().dbn_greedy_decode_ws_bytes(B, T) // 4, ), device=dev, dtype=torch.int32)
+    check(lib().dbn_greedy_decode(_AT[logits.dtype], logits.data_ptr(), B, T, C, len_ptr, _MODES[mode], ws.data_ptr(), codes.data_ptr(),
+                                  count.data_ptr(), score.data_ptr(), _stream(dev)), 'greedy_decode')
+    return codes, count, score
+
+
+def _fetch(codes, count, score=None):
+    """codes [B, T], count [B] (and score [B]) on the host from ONE device-to-host copy"""
+    parts = [codes, count[:, None]] + ([score.view(torch.int32)[:, None]] if score is not None else [])
+    host = torch.cat(parts, 1).cpu().numpy()
+    T = codes.shape[1]
+    return host[:, :T], host[:, T], (host[:, T + 1].copy().view(np.float32) if score is not None else None)
+
+
+class _LabelConverter:
+    def __init__(self, head, character):
+        self.character = list(head) + list(character)
+        self._table = np.array(self.character, dtype=object)
+
+    def decode_host(self, codes, count):
+        """numpy codes [B, T], count [B] -> list of B strings"""
+        codes, count = np.asarray(codes), np.asarray(count).astype(np.int64)
+        B, T = codes.shape
+        if count.shape != (B, ) or (count < 0).any() or (count > T).any():
+            raise ValueError('count must be [%d] within 0 .. %d' % (B, T))
+        kept = np.arange(T)[None, :] < count[:, None]
+        flat = codes[kept].astype(np.int64)
+        if flat.size and (flat.min() < 0 or flat.max() >= len(self.character)):
+            raise ValueError('codes outside the %d entries of the character table' % len(self.character))
+        chars = self._table[flat]
+        ends = np.cumsum(count)
+        return [''.join(chars[e - n:e]) for e, n in zip(ends.tolist(), count.tolist())]
+
+    def decode(self, codes, count):
+        """codes [B, T], count [B] as greedy_decode returns them (device tensors; host arrays are taken as they are) -> list of
+        B strings, from one device-to-host copy; a kept code outside the table raises ValueError"""
+        if isinstance(codes, torch.Tensor):
+            codes, count, _ = _fetch(codes, count)
+        return self.decode_host(codes, count)
+
+
+class CTCLabelConverter(_LabelConverter):
+    """table ['[blank]'] + list(character): index 0 is the CTC blank (greedy_decode mode 'ctc')"""
+
+    def __init__(self, character):
+        super().__init__(['[blank]'], character)
+
+
+class AttnLabelConverter(_LabelConverter):
+    """table ['[GO]', '[s]'] + list(character): index 1 ends a word (greedy_decode mode 'attn')"""
+
+    def __init__(self, character):
+        super().__init__(['[GO]', '[s]'], character)
+
+
+def _box_rows(boxes):
+    if isinstance(boxes, np.ndarray) and boxes.ndim == 3:
+        boxes = [boxes]
+    return [np.asarray(b[0] if isinstance(b, tuple) and len(b) == 2 else b) for b in boxes]
+
+
+def recognize_words(images, boxes, model, converter, prediction='CTC', batch_size=512, batch_max_length=25, rgb=False, size=SIZE,
+                    scores=None, min_score=None):
+    """From images and detected boxes to strings: crop_words -> words_to_input -> model -> greedy_decode -> converter.decode.
+
+    images, boxes, size, scores, min_score: as crop_words takes them.  Or ready crops: images = a uint8 device tensor
+    [K, h, w, 3] with boxes = None.  model: the user's recogniser, called under no_grad in chunks of batch_size as the
+    reference calls it, with text_for_pred a zero LongTensor [b, batch_max_length + 1]: model(image, text_for_pred) for
+    prediction 'CTC', model(image, text_for_pred, is_train=False) for 'Attn'; it returns logits [b, T, C].
+    Returns, per image, a list of {'box': the box row (int16 [4, 2]), 'pred': str, 'score': float} in box order; for ready
+    crops one flat list with 'box': None.  One device-to-host copy for all words."""
+    if 'CTC' in prediction:
+        mode = 'ctc'
+    elif 'Attn' in prediction:
+        mode = 'attn'
+    else:
+        raise ValueError("prediction must be 'CTC' or 'Attn', got %r" % (prediction, ))
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError('batch_size must be positive')
+    if boxes is None:
+        crops, index, rows, n_images = images, None, None, None
+    else:
+        crops, index = crop_words(images, boxes, size, scores, min_score)
+        rows = _box_rows(boxes)
+        n_images = 1 if isinstance(images, torch.Tensor) else len(images[1])
+    x = words_to_input(crops, rgb=rgb)
+    K = x.shape[0]
+    outs = []
+    with torch.no_grad():
+        for k0 in range(0, K, batch_size):
+            image = x[k0:k0 + batch_size]
+            text_for_pred = torch.zeros((image.shape[0], batch_max_length + 1), dtype=torch.long, device=x.device)
+            logits = model(image, text_for_pred) if mode == 'ctc' else model(image, text_for_pred, is_train=False)
+            outs.append(greedy_decode(logits, mode))
+    words = []
+    if outs:
+        T = max(c.shape[1] for c, _, _ in outs)
+        pad = [torch.nn.functional.pad(c, (0, T - c.shape[1]), value=-1) for c, _, _ in outs]
+        codes, count, score = _fetch(torch.cat(pad), torch.cat([n for _, n, _ in outs]), torch.cat([s for _, _, s in outs]))
+        words = list(zip(converter.decode_host(codes, count), score.tolist()))
+    if index is None:
+        return [{'box': None, 'pred': p, 'score': s} for p, s in words]
+    result = [[] for _ in range(n_images)]
+    for (n, k), (p, s) in zip(index.tolist(), words):
+        result[n].append({'box': rows[n][k], 'pred': p, 'score': s})
+    return result

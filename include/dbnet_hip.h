@@ -482,6 +482,25 @@ int dbn_render_paint(const unsigned char* src, unsigned char* dst, const long lo
  * float32 per image, truncated; a constant image gives zeros.  mm: 8 bytes per image of workspace. */
 int dbn_minmax_scale_u8(const float* x, int N, int H, int W, void* mm, unsigned char* out, void* stream);
 
+/* ---- around a text recogniser: rec_preprocess and predict() of test_ocr.py:59-108,179-200, batched (csrc/recognise.hip,
+ *      db_text_minimal_amd/recognise.py).  at: storage type of the floating tensor (0 fp32, 1 bf16, 2 fp16). ---- */
+/* crops [K][h][w][3] uint8 (n_px = K * h * w pixels, hw = h * w) -> out [K][1][h][w] (rgb = 0: PIL's convert('L') in
+ * integers, (19595 c0 + 38470 c1 + 7471 c2 + 32768) >> 16; bgr != 0 swaps the weights of c0 and c2) or [K][3][h][w]
+ * (rgb != 0, planar, the crop's channel order), each value lut[byte]: lut = 256 fp32 on the device, (g / 255 - 0.5) / 0.5
+ * as the caller rounds it; the 16-bit types store its round-to-nearest-even conversion.  Every element written. */
+int dbn_words_to_input(int at, const unsigned char* crops, long n_px, long hw, int rgb, int bgr, const float* lut, void* out, void* stream);
+/* bytes of workspace dbn_greedy_decode needs (8 per step) */
+long dbn_greedy_decode_ws_bytes(int B, int T);
+/* Greedy decode of logits [B][T][C] (contiguous, widened to fp32 exactly), two launches, no host synchronisation.  Per step
+ * t < len_b (lengths[b] clamped to 0 .. T; lengths NULL: T): m = max_c x, k_t = the smallest index with x == m,
+ * p_t = 1 / sum_c expf(x_c - m) in fp32; a row with a NaN gives k_t = the index of its first NaN and p_t = NaN.
+ * mode 0 (CTC): step t is kept iff k_t != 0 and (t == 0 or k_t != k_{t-1}); score = the product of p_t over all len_b steps.
+ * mode 1 (attention): the steps before the first k_t == 1 are kept; score = the product of their p_t (1.0 for none).
+ * The product is formed in fp32 in ascending t.  codes [B][T]: the kept k_t packed to the left, then -1; count [B];
+ * score [B]; every element written.  ws: dbn_greedy_decode_ws_bytes(B, T) bytes, any contents. */
+int dbn_greedy_decode(int at, const void* logits, int B, int T, int C, const int* lengths, int mode, void* ws, int* codes, int* count,
+                      float* score, void* stream);
+
 /* ---- text boxes from probability maps: boxes_from_bitmap of postprocess.py:105-141 (csrc/detect.hip,
  *      db_text_minimal_amd/postprocess.py detect_boxes).  PARITY UNPINNED against cv2 / pyclipper. ---- */
 /* One record per candidate (72 bytes):
