@@ -32,6 +32,7 @@ import torch
 
 from ._lib import check, lib
 from .gt_maps import GT_KEYS, MEAN, make_gt_maps, plan_polygons
+from .jpeg import JpegCoefficients, decode_coefficients
 
 ROTATE = (-10.0, 10.0)  # data_loaders.py:62-66
 SCALE = (0.5, 3.0)
@@ -390,8 +391,8 @@ def image_collate(items):
 
 
 class DeviceBatches:
-    """Turns each (packed, shapes, polys, tags) batch of `loader` (collate_fn=image_collate) into the dict fit / evaluate
-    consume: `img` (augment_images) and the four GT_KEYS maps (make_gt_maps), on `device`.  training=True draws the
+    """Turns each (packed, shapes, polys, tags) batch of `loader` (collate_fn=image_collate, or jpeg_collate for JPEG bytes:
+    the first element is then a JpegCoefficients and its device half runs here) into the dict fit / evaluate consume: `img` (augment_images) and the four GT_KEYS maps (make_gt_maps), on `device`.  training=True draws the
     augmentation from np.random.RandomState(seed), continued across passes; False is the letterbox, and adds `anns`
     (per image, the scaled polygons) and `ignore_tags` (per image, the GT ignore flags) as the reference's test loader
     returns them.  gt_kwargs go to make_gt_maps (shrink_ratio, thresh_min, thresh_max, min_text_size, ignore_tags)."""
@@ -406,6 +407,8 @@ class DeviceBatches:
 
     def convert(self, batch):
         packed, shapes, polys, tags = batch
+        if isinstance(packed, JpegCoefficients):  # jpeg_collate: the device half of the decode
+            packed, shapes = decode_coefficients(packed, self.device)
         if self.training:
             plans = plan_augment(shapes, polys, self.rng, self.size)
         else:

@@ -1,0 +1,709 @@
+// Baseline JPEG decode for the device pipeline, in the place of the reference's cv2.imread(path)[:, :, ::-1]
+// (data_loaders.py:78, utils.py:179): the serial, bit-granular entropy stage on the host, everything after it on the device.
+//   host    dbn_jpeg_info            markers of one stream: size, components, sampling, restart interval, Exif orientation and
+//                                    a support code; never reads past len
+//           dbn_jpeg_coef_elems      int16 coefficients a batch needs (per image and in total)
+//           dbn_jpeg_entropy_batch   Huffman-decodes N streams on up to min(N, 16, threads) threads into one int16 buffer —
+//                                    per image and component the blocks of the MCU-padded grid in raster order, 64
+//                                    coefficients each in NATURAL (de-zigzagged) order — plus an int64 descriptor per image,
+//                                    one quantisation table per component and a status per image (a corrupt file fails alone)
+//   device  dbn_jpeg_pixels          two kernels on one stream: jpeg_idct_kernel (dequantise, libjpeg's slow-integer 8 x 8
+//                                    inverse DCT, + 128, clamp -> uint8 sample planes in a workspace) and jpeg_rgb_kernel
+//                                    ("fancy" triangle chroma upsampling over the true downsampled size, YCbCr -> RGB or
+//                                    grey x 3 -> packed uint8 [H][W][3] at the descriptor's byte offset).  Mixed sizes and
+//                                    samplings run in one call: each workgroup looks its work up in a host-built table.
+// The arithmetic is libjpeg's (jidctint.c jpeg_idct_islow with CONST_BITS 13 / PASS1_BITS 2, jdsample.c h2v1 / h2v2
+// fancy upsampling — plain replication when the downsampled width is 2 or less, as jinit_upsampler chooses — and jdcolor.c's
+// 16-bit fixed-point tables), in int32; pinned bit for bit against Pillow / libjpeg-turbo through tests/jpeg_ref.py.  UNPINNED:
+// IDCT results far outside the clamp range (corrupt data), where libjpeg indexes a masked table and this file clamps.
+//
+// Supported: SOF0 and 8-bit SOF1, 1 component or 3 (YCbCr), one interleaved scan, luma sampling 1x1 / 2x1 / 2x2 with 1x1
+// chroma, DRI / RSTn, up to 4 Huffman and quantisation tables (8- or 16-bit entries), fill bytes and FF00 stuffing.  Every
+// other kind is refused with its own status code (include/dbnet_hip.h).  The parser takes untrusted bytes: every read is
+// checked against the end of the stream, and a decode writes only inside its image's slice of the coefficient buffer.
+#include <string.h>
+
+#include <atomic>
+#include <thread>
+#include <vector>
+
+#include "common.h"
+
+namespace {
+
+enum {
+    JS_OK = 0, JS_NOT_JPEG, JS_TRUNCATED, JS_PROGRESSIVE, JS_ARITHMETIC, JS_LOSSLESS, JS_PRECISION, JS_COMPONENTS, JS_SAMPLING,
+    JS_MULTISCAN, JS_BAD_HEADER, JS_BAD_CODE, JS_COEF_RUN, JS_MARKER
+};
+
+constexpr int JP_DESC = 24;  // int64 per image, see include/dbnet_hip.h
+constexpr int JP_INFO = 24;
+// descriptor fields
+enum { D_COEF = 0, D_W, D_H, D_NC, D_OUT, D_QT, D_COMP /* 4 per component: bw, bh, h, v */, D_HMAX = 18, D_VMAX, D_MCUX, D_MCUY, D_STATUS, D_RI };
+
+const unsigned char kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                   41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                   30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// ---- host: markers ------------------------------------------------------------------------------------------------------
+struct Huff {
+    bool present = false;
+    unsigned short fast[512];  // 9-bit prefix -> length << 8 | symbol, 0 when the code is longer
+    int mincode[17], maxcode[17], first[17];
+    unsigned char vals[256];
+    int nvals = 0;
+};
+
+struct Header {
+    int status = JS_OK;
+    int width = 0, height = 0, ncomp = 0, sof = -1, precision = 0, ri = 0, orientation = 0, jfif = 0, adobe = -1;
+    int cid[4] = {0, 0, 0, 0}, h[4] = {0, 0, 0, 0}, v[4] = {0, 0, 0, 0}, tq[4] = {0, 0, 0, 0};
+    bool have_qt[4] = {false, false, false, false};
+    unsigned short qt[4][64];  // natural order
+    Huff dc[4], ac[4];
+    int td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
+    long scan_start = 0;
+    // derived for a supported stream
+    int hmax = 1, vmax = 1, mcux = 0, mcuy = 0, bw[3] = {0, 0, 0}, bh[3] = {0, 0, 0}, sh[3] = {1, 1, 1}, sv[3] = {1, 1, 1};
+    long coef_elems() const {
+        long n = 0;
+        for (int c = 0; c < ncomp && c < 3; ++c) n += (long)bw[c] * bh[c] * 64;
+        return n;
+    }
+};
+
+bool build_huff(Huff& t, const unsigned char* counts, const unsigned char* vals, int nvals) {
+    memset(t.fast, 0, sizeof(t.fast));
+    t.nvals = nvals;
+    memcpy(t.vals, vals, nvals);
+    int code = 0, k = 0;
+    for (int l = 1; l <= 16; ++l) {
+        const int n = counts[l - 1];
+        if (code + n > (1 << l)) return false;
+        t.mincode[l] = code;
+        t.maxcode[l] = n ? code + n - 1 : -1;
+        t.first[l] = k;
+        if (l <= 9) {
+            for (int i = 0; i < n; ++i) {
+                const int c = (code + i) << (9 - l);
+                for (int j = 0; j < (1 << (9 - l)); ++j) t.fast[c + j] = (unsigned short)(l << 8 | vals[k + i]);
+            }
+        }
+        code = (code + n) << 1;
+        k += n;
+    }
+    t.present = true;
+    return true;
+}
+
+int exif_orientation(const unsigned char* s, long n) {
+    if (n < 14 || memcmp(s, "Exif\0\0", 6) != 0) return 0;
+    const unsigned char* t = s + 6;
+    const long tn = n - 6;
+    bool le;
+    if (t[0] == 'I' && t[1] == 'I') le = true;
+    else if (t[0] == 'M' && t[1] == 'M') le = false;
+    else return 0;
+    auto u = [&](long o, int k, long* out) {
+        if (o < 0 || o + k > tn) return false;
+        long v = 0;
+        for (int i = 0; i < k; ++i) v = v << 8 | t[le ? o + k - 1 - i : o + i];
+        *out = v;
+        return true;
+    };
+    long magic, ifd, cnt;
+    if (!u(2, 2, &magic) || magic != 42 || !u(4, 4, &ifd) || !u(ifd, 2, &cnt)) return 0;
+    for (long k = 0; k < cnt; ++k) {
+        const long e = ifd + 2 + 12 * k;
+        long tag, type, num, val;
+        if (!u(e, 2, &tag) || !u(e + 8, 2, &val)) return 0;
+        if (tag == 0x0112) {
+            if (!u(e + 2, 2, &type) || !u(e + 4, 4, &num)) return 0;
+            return (type == 3 && num == 1 && val >= 1 && val <= 8) ? (int)val : 0;
+        }
+    }
+    return 0;
+}
+
+// parses up to and including the SOS header; hd.status tells whether the scan can be decoded
+void parse_header(const unsigned char* d, long n, Header& hd) {
+    auto fail = [&](int s) { hd.status = s; };
+    if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(JS_NOT_JPEG);
+    long p = 2;
+    for (;;) {
+        if (p >= n) return fail(JS_TRUNCATED);
+        if (d[p] != 0xFF) return fail(JS_BAD_HEADER);
+        while (p < n && d[p] == 0xFF) ++p;
+        if (p >= n) return fail(JS_TRUNCATED);
+        const int m = d[p++];
+        if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
+        if (m == 0xD9) return fail(JS_BAD_HEADER);
+        if (p + 2 > n) return fail(JS_TRUNCATED);
+        const long L = d[p] << 8 | d[p + 1];
+        if (L < 2) return fail(JS_BAD_HEADER);
+        if (p + L > n) return fail(JS_TRUNCATED);
+        const unsigned char* s = d + p + 2;
+        const long sn = L - 2;
+        p += L;
+        if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
+            if (hd.sof >= 0) return fail(JS_BAD_HEADER);
+            if (m == 0xC2) return fail(JS_PROGRESSIVE);
+            if (m == 0xC9 || m == 0xCA || m == 0xCB || m == 0xCD || m == 0xCE || m == 0xCF) return fail(JS_ARITHMETIC);
+            if (m == 0xC3 || m == 0xC5 || m == 0xC6 || m == 0xC7) return fail(JS_LOSSLESS);
+            if (sn < 6) return fail(JS_BAD_HEADER);
+            hd.precision = s[0];
+            if (s[0] != 8) return fail(JS_PRECISION);
+            hd.sof = m - 0xC0;
+            hd.height = s[1] << 8 | s[2];
+            hd.width = s[3] << 8 | s[4];
+            hd.ncomp = s[5];
+            if (hd.height == 0 || hd.width == 0 || hd.ncomp == 0 || sn != 6 + 3 * hd.ncomp) return fail(JS_BAD_HEADER);
+            for (int c = 0; c < hd.ncomp && c < 4; ++c) {
+                hd.cid[c] = s[6 + 3 * c];
+                hd.h[c] = s[7 + 3 * c] >> 4;
+                hd.v[c] = s[7 + 3 * c] & 15;
+                hd.tq[c] = s[8 + 3 * c];
+            }
+        } else if (m == 0xC8) {
+            return fail(JS_BAD_HEADER);
+        } else if (m == 0xCC) {
+            return fail(JS_ARITHMETIC);
+        } else if (m == 0xC4) {
+            long q = 0;
+            while (q < sn) {
+                if (q + 17 > sn) return fail(JS_BAD_HEADER);
+                const int tc = s[q] >> 4, th = s[q] & 15;
+                int tot = 0;
+                for (int i = 0; i < 16; ++i) tot += s[q + 1 + i];
+                if (tc > 1 || th > 3 || tot > 256 || q + 17 + tot > sn) return fail(JS_BAD_HEADER);
+                if (!build_huff(tc == 0 ? hd.dc[th] : hd.ac[th], s + q + 1, s + q + 17, tot)) return fail(JS_BAD_HEADER);
+                q += 17 + tot;
+            }
+        } else if (m == 0xDB) {
+            long q = 0;
+            while (q < sn) {
+                const int pq = s[q] >> 4, tq = s[q] & 15;
+                const int need = pq ? 128 : 64;
+                if (pq > 1 || tq > 3 || q + 1 + need > sn) return fail(JS_BAD_HEADER);
+                for (int k = 0; k < 64; ++k)
+                    hd.qt[tq][kZigzag[k]] = pq ? (unsigned short)(s[q + 1 + 2 * k] << 8 | s[q + 2 + 2 * k]) : s[q + 1 + k];
+                hd.have_qt[tq] = true;
+                q += 1 + need;
+            }
+        } else if (m == 0xDD) {
+            if (sn != 2) return fail(JS_BAD_HEADER);
+            hd.ri = s[0] << 8 | s[1];
+        } else if (m == 0xE0) {
+            if (sn >= 5 && memcmp(s, "JFIF\0", 5) == 0) hd.jfif = 1;
+        } else if (m == 0xE1) {
+            if (hd.orientation == 0) hd.orientation = exif_orientation(s, sn);
+        } else if (m == 0xEE) {
+            if (sn >= 12 && memcmp(s, "Adobe", 5) == 0) hd.adobe = s[11];
+        } else if (m == 0xDA) {
+            if (hd.sof < 0 || sn < 1) return fail(JS_BAD_HEADER);
+            if ((hd.ncomp != 1 && hd.ncomp != 3) || (hd.ncomp == 3 && hd.adobe == 0)) return fail(JS_COMPONENTS);
+            if (hd.ncomp == 3) {
+                const bool luma = (hd.h[0] == 1 && hd.v[0] == 1) || (hd.h[0] == 2 && hd.v[0] == 1) || (hd.h[0] == 2 && hd.v[0] == 2);
+                if (!luma || hd.h[1] != 1 || hd.v[1] != 1 || hd.h[2] != 1 || hd.v[2] != 1) return fail(JS_SAMPLING);
+            }
+            const int ns = s[0];
+            if (ns != hd.ncomp) return fail(JS_MULTISCAN);
+            if (sn != 4 + 2 * ns) return fail(JS_BAD_HEADER);
+            for (int c = 0; c < ns; ++c) {
+                if (s[1 + 2 * c] != hd.cid[c]) return fail(JS_BAD_HEADER);
+                hd.td[c] = s[2 + 2 * c] >> 4;
+                hd.ta[c] = s[2 + 2 * c] & 15;
+                if (hd.td[c] > 3 || hd.ta[c] > 3 || hd.tq[c] > 3) return fail(JS_BAD_HEADER);
+                if (!hd.dc[hd.td[c]].present || !hd.ac[hd.ta[c]].present || !hd.have_qt[hd.tq[c]]) return fail(JS_BAD_HEADER);
+            }
+            hd.scan_start = p;
+            break;
+        }
+    }
+    if (hd.ncomp == 3) {
+        hd.hmax = hd.h[0];
+        hd.vmax = hd.v[0];
+        for (int c = 0; c < 3; ++c) hd.sh[c] = hd.h[c], hd.sv[c] = hd.v[c];
+    }
+    hd.mcux = (hd.width + 8 * hd.hmax - 1) / (8 * hd.hmax);
+    hd.mcuy = (hd.height + 8 * hd.vmax - 1) / (8 * hd.vmax);
+    for (int c = 0; c < hd.ncomp; ++c) hd.bw[c] = hd.mcux * hd.sh[c], hd.bh[c] = hd.mcuy * hd.sv[c];
+}
+
+// ---- host: the entropy-coded segment ------------------------------------------------------------------------------------
+// The stream as bits: FF00 unstuffed, fill bytes skipped, stopped at a marker or the end of the data, past which zeros are
+// supplied and counted (`fake`), so that a decode which runs into them is found out (overrun) instead of reading further.
+struct Bits {
+    const unsigned char* d;
+    long p, n;
+    unsigned long long acc = 0;
+    int bits = 0;
+    int marker = 0;  // 0 none yet, -1 end of data, else the marker's code
+    long fake = 0;
+
+    inline unsigned byte() {
+        if (marker != 0) { fake += 8; return 0; }
+        if (p >= n) { marker = -1; fake += 8; return 0; }
+        const unsigned b = d[p++];
+        if (b != 0xFF) return b;
+        for (;;) {
+            if (p >= n) { marker = -1; break; }
+            const unsigned m = d[p++];
+            if (m == 0) return 0xFF;
+            if (m != 0xFF) { marker = (int)m; break; }
+        }
+        fake += 8;
+        return 0;
+    }
+    inline void fill() {  // at least 33 bits afterwards: one code (16) and one value (16) without refilling
+        while (bits <= 32) {
+            acc = acc << 8 | byte();
+            bits += 8;
+        }
+    }
+    inline unsigned peek(int k) const { return (unsigned)(acc >> (bits - k)) & ((1u << k) - 1); }
+    inline bool overrun() const { return marker != 0 && bits < fake; }
+    // the padding bits dropped, the next thing must be a marker: its code, or a negative status
+    int end_interval() {
+        if (overrun()) return marker == -1 ? -JS_TRUNCATED : -JS_MARKER;
+        const long real = marker != 0 ? bits - fake : bits;
+        if (real >= 8) return -JS_MARKER;
+        if (marker == 0) {
+            if (p >= n) return -JS_TRUNCATED;
+            if (d[p] != 0xFF) return -JS_MARKER;
+            while (p < n && d[p] == 0xFF) ++p;
+            if (p >= n) return -JS_TRUNCATED;
+            const int m = d[p++];
+            if (m == 0) return -JS_MARKER;
+            marker = m;
+        }
+        if (marker == -1) return -JS_TRUNCATED;
+        const int m = marker;
+        acc = 0, bits = 0, fake = 0, marker = 0;
+        return m;
+    }
+};
+
+// one Huffman symbol (after fill()): -1 for a code that is in no table
+inline int huff_symbol(Bits& b, const Huff& t) {
+    const unsigned f = t.fast[b.peek(9)];
+    if (f) {
+        b.bits -= f >> 8;
+        return f & 255;
+    }
+    for (int l = 10; l <= 16; ++l) {
+        const int code = (int)b.peek(l);
+        if (t.maxcode[l] >= 0 && code >= t.mincode[l] && code <= t.maxcode[l]) {
+            const int i = t.first[l] + code - t.mincode[l];
+            if (i >= t.nvals) return -1;
+            b.bits -= l;
+            return t.vals[i];
+        }
+    }
+    return -1;
+}
+
+inline int receive_extend(Bits& b, int s) {
+    if (s == 0) return 0;
+    const int v = (int)b.peek(s);
+    b.bits -= s;
+    return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
+}
+
+// decodes the scan of a parsed, supported stream into coef[0 .. hd.coef_elems()) (zeroed here): a status
+int decode_scan(const unsigned char* d, long n, const Header& hd, short* coef) {
+    const long total = hd.coef_elems();
+    memset(coef, 0, (size_t)total * sizeof(short));
+    long comp_off[3] = {0, 0, 0};
+    for (int c = 1; c < hd.ncomp; ++c) comp_off[c] = comp_off[c - 1] + (long)hd.bw[c - 1] * hd.bh[c - 1] * 64;
+    Bits b{d, hd.scan_start, n};
+    int pred[3] = {0, 0, 0};
+    const long mcus = (long)hd.mcux * hd.mcuy;
+    long to_restart = hd.ri;
+    int next_rst = 0;
+    for (long mcu = 0; mcu < mcus; ++mcu) {
+        if (hd.ri && mcu && to_restart == 0) {
+            const int m = b.end_interval();
+            if (m < 0) return -m;
+            if (m != 0xD0 + next_rst) return JS_MARKER;
+            next_rst = (next_rst + 1) & 7;
+            pred[0] = pred[1] = pred[2] = 0;
+            to_restart = hd.ri;
+        }
+        --to_restart;
+        const long my = mcu / hd.mcux, mx = mcu - my * hd.mcux;
+        for (int c = 0; c < hd.ncomp; ++c) {
+            const Huff& dc = hd.dc[hd.td[c]];
+            const Huff& ac = hd.ac[hd.ta[c]];
+            for (int v = 0; v < hd.sv[c]; ++v)
+                for (int u = 0; u < hd.sh[c]; ++u) {
+                    const long blk = (my * hd.sv[c] + v) * hd.bw[c] + mx * hd.sh[c] + u;
+                    const long o = comp_off[c] + blk * 64;
+                    if (o < 0 || o + 64 > total) return JS_BAD_HEADER;  // cannot happen for a grid derived above
+                    short* k64 = coef + o;
+                    b.fill();
+                    int s = huff_symbol(b, dc);
+                    if (s < 0 || s > 11) return JS_BAD_CODE;
+                    pred[c] = (short)(pred[c] + receive_extend(b, s));
+                    k64[0] = (short)pred[c];
+                    int k = 1;
+                    while (k < 64) {
+                        b.fill();
+                        const int rs = huff_symbol(b, ac);
+                        if (rs < 0) return JS_BAD_CODE;
+                        const int r = rs >> 4;
+                        s = rs & 15;
+                        if (s == 0) {
+                            if (r != 15) break;
+                            k += 16;
+                            if (k > 64) return JS_COEF_RUN;
+                            continue;
+                        }
+                        k += r;
+                        if (k > 63) return JS_COEF_RUN;
+                        k64[kZigzag[k]] = (short)receive_extend(b, s);
+                        ++k;
+                    }
+                }
+        }
+        if (b.overrun()) return b.marker == -1 ? JS_TRUNCATED : JS_MARKER;
+    }
+    const int m = b.end_interval();
+    if (m < 0) return -m;
+    if (m >= 0xD0 && m <= 0xD7) return JS_MARKER;
+    return JS_OK;
+}
+
+// ---- device -------------------------------------------------------------------------------------------------------------
+struct Img {
+    long long coef, out, qt;
+    int W, H, nc, hs, vs;
+    int bw[3], bh[3];
+    long long comp_off[3];  // element offset of the component's blocks (and byte offset of its sample plane) from `coef`
+};
+
+// A descriptor is used only if everything it makes a kernel touch lies inside the buffers: the coefficient / plane range
+// [coef, coef + blocks * 64) inside coef_elems, the tables inside qt_elems, the pixels inside out_bytes, and the grids
+// large enough for the image (the Python layer passes what dbn_jpeg_entropy_batch wrote; a failed image has status != 0).
+__device__ __forceinline__ bool load_img(const long long* __restrict__ d, long coef_elems, long qt_elems, long out_bytes, Img& g) {
+    if (d[D_STATUS] != 0) return false;
+    const long long W = d[D_W], H = d[D_H], nc = d[D_NC];
+    if (W < 1 || H < 1 || W > 65535 || H > 65535 || (nc != 1 && nc != 3)) return false;
+    g.W = (int)W, g.H = (int)H, g.nc = (int)nc;
+    g.coef = d[D_COEF], g.out = d[D_OUT], g.qt = d[D_QT];
+    const long long h0 = d[D_COMP + 2], v0 = d[D_COMP + 3];
+    if (nc == 1) {
+        g.hs = g.vs = 1;
+    } else {
+        if (!((h0 == 1 && v0 == 1) || (h0 == 2 && v0 == 1) || (h0 == 2 && v0 == 2))) return false;
+        if (d[D_COMP + 6] != 1 || d[D_COMP + 7] != 1 || d[D_COMP + 10] != 1 || d[D_COMP + 11] != 1) return false;
+        g.hs = (int)h0, g.vs = (int)v0;
+    }
+    long long blocks = 0;
+    for (int c = 0; c < 3; ++c) {
+        g.bw[c] = g.bh[c] = 0;
+        g.comp_off[c] = blocks * 64;
+        if (c >= nc) continue;
+        const long long bw = d[D_COMP + 4 * c], bh = d[D_COMP + 4 * c + 1];
+        const int cw = c == 0 ? g.W : (g.W + g.hs - 1) / g.hs, ch = c == 0 ? g.H : (g.H + g.vs - 1) / g.vs;
+        if (bw < 1 || bh < 1 || bw > 16384 || bh > 16384 || bw * 8 < cw || bh * 8 < ch) return false;
+        g.bw[c] = (int)bw, g.bh[c] = (int)bh;
+        blocks += bw * bh;
+    }
+    if (nc == 3 && (g.bw[1] != g.bw[2] || g.bh[1] != g.bh[2])) return false;  // the chroma planes share one pitch
+    if (g.coef < 0 || (g.coef & 63) || g.coef + blocks * 64 > coef_elems) return false;
+    if (g.qt < 0 || (g.qt & 63) || g.qt + nc * 64 > qt_elems) return false;
+    if (g.out < 0 || g.out + (long long)g.W * g.H * 3 > out_bytes) return false;
+    return true;
+}
+
+__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// jpeg_idct_islow's one-dimensional pass on eight values (CONST_BITS = 13); SHIFT 11 for columns, 18 for rows
+template <int SHIFT>
+__device__ __forceinline__ void idct_1d(const int (&i)[8], int (&o)[8]) {
+    int z2 = i[2], z3 = i[6];
+    int z1 = (z2 + z3) * 4433;
+    int tmp2 = z1 + z3 * (-15137), tmp3 = z1 + z2 * 6270;
+    int tmp0 = (int)((unsigned)(i[0] + i[4]) << 13), tmp1 = (int)((unsigned)(i[0] - i[4]) << 13);
+    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    tmp0 = i[7], tmp1 = i[5], tmp2 = i[3], tmp3 = i[1];
+    z1 = tmp0 + tmp3, z2 = tmp1 + tmp2, z3 = tmp0 + tmp2;
+    int z4 = tmp1 + tmp3;
+    const int z5 = (z3 + z4) * 9633;
+    tmp0 *= 2446, tmp1 *= 16819, tmp2 *= 25172, tmp3 *= 12299;
+    z1 *= -7373, z2 *= -20995, z3 = z3 * (-16069) + z5, z4 = z4 * (-3196) + z5;
+    tmp0 += z1 + z3, tmp1 += z2 + z4, tmp2 += z2 + z3, tmp3 += z1 + z4;
+    constexpr int R = 1 << (SHIFT - 1);
+    o[0] = (tmp10 + tmp3 + R) >> SHIFT, o[7] = (tmp10 - tmp3 + R) >> SHIFT;
+    o[1] = (tmp11 + tmp2 + R) >> SHIFT, o[6] = (tmp11 - tmp2 + R) >> SHIFT;
+    o[2] = (tmp12 + tmp1 + R) >> SHIFT, o[5] = (tmp12 - tmp1 + R) >> SHIFT;
+    o[3] = (tmp13 + tmp0 + R) >> SHIFT, o[4] = (tmp13 - tmp0 + R) >> SHIFT;
+}
+
+// ---- kernel 1: coefficients -> sample planes --------------------------------------------------------------------------------
+// A workgroup takes ID_BLOCKS consecutive blocks of one component of one image (tab[wg] = {image, component, first block}); a
+// wave takes eight of them, eight lanes per block.  Lane j of a block loads coefficient row j and table row j as one
+// 16-byte vector each and multiplies; the products cross to the lanes as columns through LDS (block stride 72 dwords, row
+// stride 9: neither the row-wise stores nor the column-wise loads meet a bank twice), lane j runs column j, the results
+// cross back the same way, lane j runs row j and stores its eight samples as one 8-byte vector into the plane.
+constexpr int ID_THREADS = 256, ID_BLOCKS = ID_THREADS / 8, ID_BSTRIDE = 72, ID_RSTRIDE = 9;
+typedef short short8 __attribute__((ext_vector_type(8)));
+typedef unsigned short ushort8 __attribute__((ext_vector_type(8)));
+
+__global__ void __launch_bounds__(ID_THREADS) jpeg_idct_kernel(const short* __restrict__ coef, long coef_elems,
+                                                                const long long* __restrict__ desc, int N,
+                                                                const unsigned short* __restrict__ qtabs, long qt_elems,
+                                                                const int* __restrict__ tab, long out_bytes,
+                                                                unsigned char* __restrict__ planes) {
+    __shared__ int s_t[ID_BLOCKS * ID_BSTRIDE];
+    const int n = tab[4 * blockIdx.x], c = tab[4 * blockIdx.x + 1], blk0 = tab[4 * blockIdx.x + 2];
+    Img g;
+    bool ok = n >= 0 && n < N && c >= 0 && c < 3 && blk0 >= 0 && load_img(desc + (long)n * JP_DESC, coef_elems, qt_elems, out_bytes, g);
+    ok = ok && c < g.nc;
+    const int t = threadIdx.x, lb = t >> 3, j = t & 7;
+    const long nblk = ok ? (long)g.bw[c] * g.bh[c] : 0;
+    const long blk = (long)blk0 + lb;
+    const bool live = ok && blk < nblk;
+    int a[8], o[8];
+    if (live) {
+        const short8 k = *reinterpret_cast<const short8*>(coef + g.coef + g.comp_off[c] + blk * 64 + j * 8);
+        const ushort8 q = *reinterpret_cast<const ushort8*>(qtabs + g.qt + c * 64 + j * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[e] = (int)k[e] * (int)q[e];
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[e] = 0;
+    }
+    int* sb = s_t + lb * ID_BSTRIDE;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sb[j * ID_RSTRIDE + e] = a[e];
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] = sb[e * ID_RSTRIDE + j];  // column j
+    idct_1d<11>(a, o);
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sb[e * ID_RSTRIDE + j] = o[e];
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] = sb[j * ID_RSTRIDE + e];  // row j
+    idct_1d<18>(a, o);
+    if (!live) return;
+    unsigned lo = 0, hi = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        lo |= (unsigned)clamp255(o[e] + 128) << (8 * e);
+        hi |= (unsigned)clamp255(o[e + 4] + 128) << (8 * e);
+    }
+    const long by = blk / g.bw[c], bx = blk - by * g.bw[c];
+    unsigned char* dst = planes + g.coef + g.comp_off[c] + (by * 8 + j) * ((long)g.bw[c] * 8) + bx * 8;
+    *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
+}
+
+// ---- kernel 2: sample planes -> packed RGB -----------------------------------------------------------------------------------
+// A workgroup owns RGB_PX consecutive pixels of one image's output run (tab[wg] = {image, chunk}; they may span rows), a lane
+// four consecutive ones: it upsamples their chroma, converts, packs the twelve bytes into three dwords and puts them
+// into LDS; the run then leaves as aligned dwords, with single bytes only at a run's unaligned ends (the packed layout
+// gives an image's first byte any alignment).
+constexpr int RGB_THREADS = 256, RGB_PPT = 4, RGB_PX = RGB_THREADS * RGB_PPT;
+
+// one chroma sample at full-resolution (x, y): jdsample.c h2v1_fancy_upsample / h2v2_fancy_upsample over the true
+// downsampled size cw x ch; fullsize for 1 x 1; replication when cw <= 2
+__device__ __forceinline__ int chroma_at(const unsigned char* __restrict__ P, int pitch, int cw, int ch, int hs, int vs, int x, int y) {
+    if (hs == 1) return P[(long)y * pitch + x];
+    const int i = x >> 1, r = vs == 2 ? y >> 1 : y;
+    const unsigned char* near = P + (long)r * pitch;
+    if (cw <= 2) return near[i];
+    const int odd = x & 1;
+    const int i2 = odd ? i + 1 : i - 1;  // the other column, when inside
+    const bool edge = i2 < 0 || i2 >= cw;
+    if (vs == 1) {
+        if (edge) return near[i];
+        return (3 * near[i] + near[i2] + (odd ? 2 : 1)) >> 2;
+    }
+    int fr = (y & 1) ? r + 1 : r - 1;
+    fr = fr < 0 ? 0 : (fr >= ch ? ch - 1 : fr);
+    const unsigned char* far = P + (long)fr * pitch;
+    const int t = 3 * near[i] + far[i];
+    if (edge) return (4 * t + (odd ? 7 : 8)) >> 4;
+    const int t2 = 3 * near[i2] + far[i2];
+    return (3 * t + t2 + (odd ? 7 : 8)) >> 4;
+}
+
+__global__ void __launch_bounds__(RGB_THREADS) jpeg_rgb_kernel(const unsigned char* __restrict__ planes, long coef_elems,
+                                                                const long long* __restrict__ desc, int N, long qt_elems,
+                                                                const int* __restrict__ tab, unsigned char* __restrict__ out,
+                                                                long out_bytes) {
+    __shared__ unsigned int s_out[RGB_PX * 3 / 4];
+    const int n = tab[4 * blockIdx.x], chunk = tab[4 * blockIdx.x + 1];
+    Img g;
+    if (!(n >= 0 && n < N && chunk >= 0 && load_img(desc + (long)n * JP_DESC, coef_elems, qt_elems, out_bytes, g))) return;
+    const long npx = (long)g.W * g.H, p0 = (long)chunk * RGB_PX;
+    if (p0 >= npx) return;
+    const int t = threadIdx.x;
+    const unsigned char* PY = planes + g.coef;
+    const unsigned char* PB = PY + g.comp_off[1];
+    const unsigned char* PR = PY + g.comp_off[2];
+    const int pitchY = g.bw[0] * 8, pitchC = g.bw[1] * 8;
+    const int cw = (g.W + g.hs - 1) / g.hs, ch = (g.H + g.vs - 1) / g.vs;
+    const long q0 = p0 + (long)t * RGB_PPT;
+    int y = (int)(q0 / g.W), x = (int)(q0 - (long)y * g.W);
+    unsigned char px[12];
+#pragma unroll
+    for (int e = 0; e < RGB_PPT; ++e) {
+        int r = 0, gg = 0, b = 0;
+        if (q0 + e < npx) {
+            const int Y = PY[(long)y * pitchY + x];
+            if (g.nc == 1) {
+                r = gg = b = Y;
+            } else {
+                const int cb = chroma_at(PB, pitchC, cw, ch, g.hs, g.vs, x, y) - 128;
+                const int cr = chroma_at(PR, pitchC, cw, ch, g.hs, g.vs, x, y) - 128;
+                r = clamp255(Y + ((91881 * cr + 32768) >> 16));
+                gg = clamp255(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+                b = clamp255(Y + ((116130 * cb + 32768) >> 16));
+            }
+        }
+        px[3 * e] = (unsigned char)r, px[3 * e + 1] = (unsigned char)gg, px[3 * e + 2] = (unsigned char)b;
+        if (++x == g.W) x = 0, ++y;
+    }
+#pragma unroll
+    for (int w = 0; w < 3; ++w)
+        s_out[t * 3 + w] = px[4 * w] | (unsigned)px[4 * w + 1] << 8 | (unsigned)px[4 * w + 2] << 16 | (unsigned)px[4 * w + 3] << 24;
+    __syncthreads();
+    const unsigned char* sb = reinterpret_cast<const unsigned char*>(s_out);
+    const long b0 = p0 * 3;
+    const int nb = (int)min((long)RGB_PX * 3, npx * 3 - b0);
+    unsigned char* o = out + g.out + b0;
+    const int head = (int)((4 - (reinterpret_cast<size_t>(o) & 3)) & 3);  // bytes before the first aligned dword
+    const int lead = head < nb ? head : nb;
+    const int nd = (nb - lead) >> 2, tail0 = lead + 4 * nd;
+    if (t < lead) o[t] = sb[t];
+    if (t >= 32 && t - 32 < nb - tail0) o[tail0 + t - 32] = sb[tail0 + t - 32];
+    unsigned int* o4 = reinterpret_cast<unsigned int*>(o + lead);
+    if (lead == 0) {
+        for (int i = t; i < nd; i += RGB_THREADS) o4[i] = s_out[i];
+    } else {
+        for (int i = t; i < nd; i += RGB_THREADS) {
+            const unsigned char* s = sb + lead + 4 * i;
+            o4[i] = s[0] | (unsigned)s[1] << 8 | (unsigned)s[2] << 16 | (unsigned)s[3] << 24;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// out[24]: 0 status (support code), 1 width, 2 height, 3 components, 4 restart interval, 5 Exif orientation (0 none),
+// 6 + 2c / 7 + 2c sampling factors h / v of component c (c < 4), 14 SOF type (0 baseline, 1 extended; -1 unknown),
+// 15 int16 coefficients the stream needs (0 unless supported), 16 JFIF marker seen, 17 Adobe transform (-1 no marker),
+// 18 sample precision
+int dbn_jpeg_info(const unsigned char* data, long len, long long* out) {
+    DBN_REQUIRE(data && out && len >= 0);
+    Header* hd = new Header;
+    parse_header(data, len, *hd);
+    for (int i = 0; i < JP_INFO; ++i) out[i] = 0;
+    out[0] = hd->status, out[1] = hd->width, out[2] = hd->height, out[3] = hd->ncomp, out[4] = hd->ri, out[5] = hd->orientation;
+    for (int c = 0; c < 4; ++c) out[6 + 2 * c] = hd->h[c], out[7 + 2 * c] = hd->v[c];
+    out[14] = hd->sof, out[15] = hd->status == JS_OK ? hd->coef_elems() : 0, out[16] = hd->jfif, out[17] = hd->adobe;
+    out[18] = hd->precision;
+    delete hd;
+    return DBN_OK;
+}
+
+// per_image[n] = int16 coefficients of stream n = blob[offs[n] .. offs[n + 1]) (0 for one that cannot be decoded); the sum
+long dbn_jpeg_coef_elems(const unsigned char* blob, const long long* offs, int N, long long* per_image) {
+    if (!blob || !offs || N < 0) return -1;
+    long total = 0;
+    Header* hd = new Header;
+    for (int n = 0; n < N; ++n) {
+        *hd = Header();
+        long e = 0;
+        if (offs[n] >= 0 && offs[n + 1] >= offs[n]) {
+            parse_header(blob + offs[n], (long)(offs[n + 1] - offs[n]), *hd);
+            if (hd->status == JS_OK) e = hd->coef_elems();
+        }
+        if (per_image) per_image[n] = e;
+        total += e;
+    }
+    delete hd;
+    return total;
+}
+
+// coef: coef_elems int16 (dbn_jpeg_coef_elems); desc: int64 [N][24]; qtabs: uint16 [N][3][64] (natural order, one table per
+// component); status: int [N].  Image n's coefficients start at the sum of the counts before it, its pixels at the sum of the
+// H * W * 3 of the decodable headers before it.  An image whose scan fails keeps its slots (zeroed) and a status != 0.
+int dbn_jpeg_entropy_batch(const unsigned char* blob, const long long* offs, int N, short* coef, long coef_elems, long long* desc,
+                           unsigned short* qtabs, int* status, int threads) {
+    DBN_REQUIRE(blob && offs && desc && qtabs && status && N > 0 && coef_elems >= 0 && (coef || coef_elems == 0));
+    for (int n = 0; n < N; ++n) DBN_REQUIRE(offs[n] >= 0 && offs[n + 1] >= offs[n]);
+    std::vector<Header> hds((size_t)N);
+    long co = 0, oo = 0;
+    for (int n = 0; n < N; ++n) {
+        Header& hd = hds[n];
+        parse_header(blob + offs[n], (long)(offs[n + 1] - offs[n]), hd);
+        long long* d = desc + (long)n * JP_DESC;
+        for (int i = 0; i < JP_DESC; ++i) d[i] = 0;
+        unsigned short* q = qtabs + (long)n * 192;
+        memset(q, 0, 192 * sizeof(unsigned short));
+        d[D_STATUS] = status[n] = hd.status;
+        d[D_COEF] = co, d[D_OUT] = oo, d[D_QT] = (long)n * 192;
+        if (hd.status != JS_OK) continue;
+        if (co + hd.coef_elems() > coef_elems) return DBN_ERR_ARG;
+        d[D_W] = hd.width, d[D_H] = hd.height, d[D_NC] = hd.ncomp;
+        for (int c = 0; c < hd.ncomp; ++c) {
+            d[D_COMP + 4 * c] = hd.bw[c], d[D_COMP + 4 * c + 1] = hd.bh[c], d[D_COMP + 4 * c + 2] = hd.sh[c], d[D_COMP + 4 * c + 3] = hd.sv[c];
+            memcpy(q + 64 * c, hd.qt[hd.tq[c]], 64 * sizeof(unsigned short));
+        }
+        d[D_HMAX] = hd.hmax, d[D_VMAX] = hd.vmax, d[D_MCUX] = hd.mcux, d[D_MCUY] = hd.mcuy, d[D_RI] = hd.ri;
+        co += hd.coef_elems();
+        oo += (long)hd.width * hd.height * 3;
+    }
+    int T = threads < 1 ? 1 : threads;
+    T = T > 16 ? 16 : T;
+    T = T > N ? N : T;
+    std::atomic<int> next(0);
+    auto work = [&]() {
+        for (;;) {
+            const int n = next.fetch_add(1);
+            if (n >= N) return;
+            if (hds[n].status != JS_OK) continue;
+            long long* d = desc + (long)n * JP_DESC;
+            const int s = decode_scan(blob + offs[n], (long)(offs[n + 1] - offs[n]), hds[n], coef + d[D_COEF]);
+            if (s != JS_OK) {
+                memset(coef + d[D_COEF], 0, (size_t)hds[n].coef_elems() * sizeof(short));
+                d[D_STATUS] = status[n] = s;
+            }
+        }
+    };
+    if (T == 1) {
+        work();
+    } else {
+        std::vector<std::thread> pool;
+        for (int i = 1; i < T; ++i) pool.emplace_back(work);
+        work();
+        for (auto& th : pool) th.join();
+    }
+    return DBN_OK;
+}
+
+// coef / desc / qtabs: the outputs of dbn_jpeg_entropy_batch, on the device; tab_idct int32 [n_idct][4] = {image, component,
+// first block, 0} (one workgroup per 32 blocks), tab_rgb int32 [n_rgb][4] = {image, chunk of 1024 pixels, 0, 0}; planes: a
+// workspace of coef_elems bytes; out: out_bytes bytes, every pixel of every image with status 0 written once.
+int dbn_jpeg_pixels(const short* coef, long coef_elems, const long long* desc, const unsigned short* qtabs, int N, const int* tab_idct,
+                    int n_idct, const int* tab_rgb, int n_rgb, unsigned char* planes, unsigned char* out, long out_bytes, void* stream) {
+    DBN_REQUIRE(coef && desc && qtabs && tab_idct && tab_rgb && planes && out && N > 0 && n_idct > 0 && n_rgb > 0 && coef_elems > 0 &&
+                out_bytes > 0);
+    DBN_REQUIRE((reinterpret_cast<size_t>(coef) & 15) == 0 && (reinterpret_cast<size_t>(qtabs) & 15) == 0 &&
+                (reinterpret_cast<size_t>(planes) & 7) == 0);
+    const long qt_elems = (long)N * 192;
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)n_idct), dim3(ID_THREADS), 0, (hipStream_t)stream, coef, coef_elems, desc, N, qtabs,
+                       qt_elems, tab_idct, out_bytes, planes);
+    hipLaunchKernelGGL(jpeg_rgb_kernel, dim3((unsigned)n_rgb), dim3(RGB_THREADS), 0, (hipStream_t)stream, planes, coef_elems, desc, N, qt_elems,
+                       tab_rgb, out, out_bytes);
+    return dbn_status();
+}
+
+}  // extern "C"

@@ -828,6 +828,30 @@ int dbn_head_tail_bwd_t(int at, const void* xb, const void* xt, const float* wb,
                         const float* bn_rstd_t, float* bn_sums, void* dxb, void* dxt, float* dw_b, float* dbias_b, float* dw_t,
                         float* dbias_t, int N, int Hq, int Wq, int channels, float kstep, float grad_scale, float* ws, void* stream);
 
+/* ---- JPEG decode for the device pipeline (csrc/jpeg.hip): in the place of cv2.imread(path)[:, :, ::-1] (data_loaders.py:78, utils.py:179).
+ * The entropy stage runs on the host, the rest (dequantise, libjpeg's slow-integer IDCT, fancy chroma upsampling, YCbCr -> RGB) on the device.
+ * Status / support codes: 0 ok, 1 not a JPEG, 2 truncated, 3 progressive (SOF2), 4 arithmetic coding, 5 lossless / hierarchical, 6 sample
+ * precision not 8 bits (12-bit), 7 4-component / Adobe-transform, 8 unsupported sampling factors, 9 non-interleaved multi-scan, 10 malformed
+ * header or missing table, 11 invalid Huffman code, 12 coefficient run past index 63, 13 entropy data and markers disagree.
+ * dbn_jpeg_info: out[24] = {status, width, height, components, restart interval, Exif orientation (0: none), h0, v0, h1, v1, h2, v2, h3, v3,
+ * SOF type, int16 coefficients needed (0 unless status 0), JFIF seen, Adobe transform (-1: no marker), precision, 0...}; reads data[0 .. len) only.
+ * dbn_jpeg_coef_elems: streams n = blob[offs[n] .. offs[n + 1]); per_image[n] (may be NULL) and the returned sum count int16 coefficients.
+ * dbn_jpeg_entropy_batch: Huffman-decodes the N streams on min(N, 16, threads) threads.  coef: per image and component the blocks of the
+ * MCU-padded grid in raster order, 64 coefficients each in NATURAL order; desc int64 [N][24] = {coefficient offset (elements), width, height,
+ * components, output byte offset, table offset (elements of qtabs), then per component c < 3 {block columns, block rows, h, v}, hmax, vmax,
+ * MCU columns, MCU rows, status, restart interval}; qtabs uint16 [N][3][64] natural order, one per component; status int [N].  A stream that
+ * fails keeps its (zeroed) slots and fails alone.
+ * dbn_jpeg_pixels: the device stage, two launches on `stream`: packed uint8 [H][W][3] RGB per image at its output byte offset (grey replicated).
+ * tab_idct int32 [n_idct][4] = {image, component, first block, 0}, one entry per 32 blocks; tab_rgb int32 [n_rgb][4] = {image, chunk of 1024
+ * pixels, 0, 0}; planes: coef_elems bytes of workspace; coef and qtabs 16-byte aligned, planes 8-byte aligned.  Descriptors that would leave a
+ * buffer are skipped. */
+int dbn_jpeg_info(const unsigned char* data, long len, long long* out);
+long dbn_jpeg_coef_elems(const unsigned char* blob, const long long* offs, int N, long long* per_image);
+int dbn_jpeg_entropy_batch(const unsigned char* blob, const long long* offs, int N, short* coef, long coef_elems, long long* desc,
+                           unsigned short* qtabs, int* status, int threads);
+int dbn_jpeg_pixels(const short* coef, long coef_elems, const long long* desc, const unsigned short* qtabs, int N, const int* tab_idct,
+                    int n_idct, const int* tab_rgb, int n_rgb, unsigned char* planes, unsigned char* out, long out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
