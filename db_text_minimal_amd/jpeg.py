@@ -1,4 +1,4 @@
-"""JPEG decode in front of the device pipeline, in the place of the reference's cv2.imread(path)[:, :, ::-1]
+"""JPEG at both ends of the device pipeline.  Decode in front of it, in the place of the reference's cv2.imread(path)[:, :, ::-1]
 (data_loaders.py:78, utils.py:179): the Huffman stage on the host in C++ (threaded over the images of a batch, no GIL), the
 rest — dequantisation, libjpeg's slow-integer inverse DCT, fancy chroma upsampling, YCbCr -> RGB — as gfx950 kernels that
 write the packed uint8 layout augment_images, crop_words and draw_outlines take (csrc/jpeg.hip).  Bit for bit libjpeg's
@@ -12,10 +12,23 @@ baseline decode (pinned against Pillow / libjpeg-turbo, tests/test_jpeg_cpu.py).
   jpeg_collate(items)                      collate_fn for items (jpeg bytes, polys, tags): the host half in the worker;
                                            DeviceBatches.convert runs the device half
 
+Encode behind it, in the place of the reference's imageio / Pillow writes (utils.py:225,272,280, test_ocr.py:176,210,
+ts_request.py:38-39): the decoder turned round (csrc/jpeg_enc.hip).  Colour conversion, chroma downsampling, libjpeg's
+slow-integer forward DCT and quantisation run as gfx950 kernels, Huffman coding (Annex K tables) on the host threads;
+JpegCoefficients is the hand-over in both directions.  Bit for bit libjpeg's baseline output for the same settings
+(pinned against Pillow / libjpeg-turbo, tests/test_jpeg_encode_cpu.py).
+
+  quant_tables(quality)                    -> uint16 [2, 64] (jpeg_set_quality's scaling of the Annex K tables)
+  forward_coefficients(images, ...)        -> JpegCoefficients (device half; decode_coefficients(...) of it is the lossy round trip)
+  entropy_encode(obj, restart_interval)    -> [bytes] (host half; runs anywhere; entropy_encode(entropy_decode(x)) transcodes losslessly)
+  encode_jpeg_batch(images, ...)           -> [bytes]; encode_jpeg(image, ...) -> bytes; save_jpegs(paths, images, ...) writes files
+
 Supported: baseline and 8-bit extended sequential Huffman streams, grey or YCbCr, 4:4:4 / 4:2:2 / 4:2:0, restart markers.
 Every other kind raises UnsupportedJpeg(reason); a damaged stream raises CorruptJpeg.  The Exif orientation is reported
 (jpeg_info(...)['orientation']) and NOT applied: PIL does not apply it either, cv2.imread does.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -82,8 +95,21 @@ class JpegCoefficients:
     [N, 3, 64], `status` int32 [N] (0: decoded) and `shapes` [(H, W)] ((0, 0) for an image that failed).  Layouts:
     include/dbnet_hip.h.  Picklable, and pin_memory() makes it what a DataLoader with pin_memory=True hands on."""
 
+    ready = None  # forward_coefficients: the event after which the pinned `coef` holds the device's result
+
     def __init__(self, coef, desc, qtabs, status):
         self.coef, self.desc, self.qtabs, self.status = coef, desc, qtabs, status
+
+    def wait(self):
+        """block the host until `coef` is filled (a result of forward_coefficients arrives on its stream)"""
+        if self.ready is not None:
+            self.ready.synchronize()
+            self.ready = None
+        return self
+
+    def __getstate__(self):
+        self.wait()
+        return dict(self.__dict__)
 
     @property
     def shapes(self):
@@ -169,6 +195,8 @@ def decode_coefficients(obj, device=None):
     hdesc = obj.desc.copy()  # pixels of the decoded images only, packed: an image whose scan failed gives its slot up
     hdesc[:, _D_OUT] = np.concatenate([[0], np.cumsum([h * w * 3 for h, w in shapes])[:-1]])
     with torch.cuda.device(dev):
+        if obj.ready is not None:  # coefficients still on their way from forward_coefficients' stream
+            torch.cuda.current_stream(dev).wait_event(obj.ready)
         coef = obj.coef.to(dev, non_blocking=True)
         desc, qt, a, b = _up(hdesc, dev), _up(obj.qtabs.view(np.int16), dev), _up(ta, dev), _up(tb, dev)
         planes = torch.empty(coef.numel(), dtype=torch.uint8, device=dev)
@@ -256,3 +284,254 @@ def jpeg_collate(items):
     polys = [[np.asarray(p, dtype=np.float64).reshape(-1, 2) for p in b[1]] for b in items]
     tags = [list(b[2]) if b[2] is not None else [None] * len(b[1]) for b in items]
     return obj, obj.shapes, polys, tags
+
+
+# ---- encode ----------------------------------------------------------------------------------------------------------
+SUBSAMPLING = {'444': (1, 1), '422': (2, 1), '420': (2, 2)}
+PLANE_CELLS, FDCT_BLOCKS = 256, 32  # per workgroup (csrc/jpeg_enc.hip)
+ENCODE_REASONS = {
+    1: 'the image was not decoded, there are no coefficients to code', 2: 'descriptor and coefficient buffer disagree',
+    3: 'a quantisation value lies outside 1 .. 255', 4: 'a DC difference needs more than 11 bits: not baseline-codable',
+    5: 'an AC coefficient needs more than 10 bits: not baseline-codable', 6: 'the output slot is too small',
+}
+# Annex K.1 / K.2, natural order
+_BASE_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+              18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100,
+              103, 99)
+_BASE_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99,
+                99) + (99, ) * 32
+
+
+class JpegEncodeError(ValueError):
+    """an image that was not encoded: .index its place in the batch, .code the status of dbn_jpeg_encode_batch, .reason"""
+
+    def __init__(self, index, reason, code=None):
+        self.index, self.reason, self.code = index, reason, code
+        ValueError.__init__(self, 'image %d: %s' % (index, reason))
+
+
+def quant_tables(quality):
+    """libjpeg's jpeg_set_quality(quality, force_baseline): the Annex K luma and chroma tables scaled by 5000 / q (q < 50) or
+    200 - 2 q percent, rounded, clamped to 1 .. 255 -> uint16 [2, 64] in natural order.  quality: 1 .. 100."""
+    if isinstance(quality, bool) or int(quality) != quality or not 1 <= int(quality) <= 100:
+        raise ValueError('quality must be an integer in 1 .. 100, got %r' % (quality, ))
+    q = int(quality)
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    base = np.array([_BASE_LUMA, _BASE_CHROMA], np.int64)
+    return np.clip((base * scale + 50) // 100, 1, 255).astype(np.uint16)
+
+
+def _tables(quality, qtables):
+    if qtables is None:
+        return quant_tables(quality)
+    t = np.asarray(qtables)
+    if t.dtype.kind not in 'iu' or t.ndim != 2 or t.shape[1] != 64 or not 1 <= t.shape[0] <= 3 or t.min() < 1 or t.max() > 255:
+        raise ValueError('qtables must be 1 to 3 integer tables of 64 values in 1 .. 255 (natural order)')
+    return t.astype(np.uint16)
+
+
+def _flat_u8(a, dev):
+    t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        raise ValueError('images must be uint8 tensors or arrays')
+    return t.contiguous().view(-1).to(dev, non_blocking=True)
+
+
+def _encode_inputs(images, shapes, dev):
+    """-> (uint8 1-D device tensor, [(byte offset, H, W, components)])"""
+    if shapes is not None:
+        if not (isinstance(images, torch.Tensor) and images.dim() == 1):
+            raise ValueError('with shapes, images is the packed 1-D uint8 batch')
+        items, o = [], 0
+        for h, w in shapes:
+            items.append((o, int(h), int(w), 3))
+            o += int(h) * int(w) * 3
+        if o != images.numel():
+            raise ValueError('packed holds %d bytes, the shapes need %d' % (images.numel(), o))
+        flat = _flat_u8(images, dev)
+    elif isinstance(images, (list, tuple)):
+        parts, items, o = [], [], 0
+        for a in images:
+            if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
+                raise ValueError('an image of a list is uint8 [H, W] or [H, W, 3], got %s' % (tuple(a.shape), ))
+            nc = 1 if a.ndim == 2 else 3
+            parts.append(_flat_u8(a, dev))
+            items.append((o, int(a.shape[0]), int(a.shape[1]), nc))
+            o += parts[-1].numel()
+        if not parts:
+            raise ValueError('no images')
+        flat = parts[0] if len(parts) == 1 else torch.cat(parts)
+    else:
+        a = images
+        nd, sh = a.ndim, tuple(int(v) for v in a.shape)
+        if nd == 2:
+            n, h, w, nc = 1, sh[0], sh[1], 1
+        elif nd == 3 and sh[2] == 3:  # one RGB image (a grey stack of width 3 goes in as a list)
+            n, h, w, nc = 1, sh[0], sh[1], 3
+        elif nd == 3:
+            n, h, w, nc = sh[0], sh[1], sh[2], 1
+        elif nd == 4 and sh[3] == 3:
+            n, h, w, nc = sh[0], sh[1], sh[2], 3
+        else:
+            raise ValueError('images must be uint8 [H, W], [N, H, W], [H, W, 3] or [N, H, W, 3], got %s' % (sh, ))
+        if n < 1:
+            raise ValueError('no images')
+        items = [(i * h * w * nc, h, w, nc) for i in range(n)]
+        flat = _flat_u8(a, dev)
+    for _, h, w, _ in items:
+        if not (1 <= h <= 65535 and 1 <= w <= 65535):
+            raise ValueError('a JPEG image is 1 .. 65535 pixels on a side, got %d x %d' % (h, w))
+    return flat, items
+
+
+def _expand(counts):
+    """counts [K] -> (owner of each of the sum(counts) entries, its index within the owner)"""
+    counts = np.asarray(counts, np.int64)
+    owner = np.repeat(np.arange(len(counts)), counts)
+    return owner, np.arange(int(counts.sum())) - np.repeat(np.cumsum(counts) - counts, counts)
+
+
+def forward_plan(items, subsampling, tables):
+    """host: the descriptors, tables and work tables of dbn_jpeg_forward for images (offset, H, W, components) ->
+    (desc int64 [N, 24] with the input byte offset in field 4, qtabs uint16 [N, 3, 64], coefficient count,
+    int32 [n_planes, 4] {image, chunk of 256 cells}, int32 [n_fdct, 4] {image, component, first block})"""
+    if subsampling not in SUBSAMPLING:
+        raise ValueError("subsampling is '444', '422' or '420', got %r" % (subsampling, ))
+    it = np.asarray(items, np.int64).reshape(-1, 4)
+    N = len(it)
+    off, H, W, nc = it[:, 0], it[:, 1], it[:, 2], it[:, 3]
+    hs = np.where(nc == 3, SUBSAMPLING[subsampling][0], 1)
+    vs = np.where(nc == 3, SUBSAMPLING[subsampling][1], 1)
+    mcux, mcuy = -(-W // (8 * hs)), -(-H // (8 * vs))
+    desc = np.zeros((N, _DESC), np.int64)
+    desc[:, _D_W], desc[:, _D_H], desc[:, _D_NC], desc[:, _D_OUT], desc[:, _D_QT] = W, H, nc, off, np.arange(N) * 192
+    blocks = np.zeros((N, 3), np.int64)
+    for c in range(3):
+        on = nc > c
+        h, v = (hs, vs) if c == 0 else (1, 1)
+        desc[:, _D_COMP + 4 * c] = np.where(on, mcux * h, 0)
+        desc[:, _D_COMP + 4 * c + 1] = np.where(on, mcuy * v, 0)
+        desc[:, _D_COMP + 4 * c + 2] = np.where(on, h, 0)
+        desc[:, _D_COMP + 4 * c + 3] = np.where(on, v, 0)
+        blocks[:, c] = np.where(on, mcux * h * mcuy * v, 0)
+    desc[:, 18], desc[:, 19], desc[:, 20], desc[:, 21] = hs, vs, mcux, mcuy
+    per = blocks.sum(1) * 64
+    desc[:, _D_COEF] = np.cumsum(per) - per
+    qtabs = np.zeros((N, 3, 64), np.uint16)
+    for c in range(3):
+        qtabs[nc > c, c] = tables[min(c, len(tables) - 1)]
+    n, chunk = _expand(-(-(mcux * 8 * mcuy * 8) // PLANE_CELLS))
+    tp = np.zeros((len(n), 4), np.int32)
+    tp[:, 0], tp[:, 1] = n, chunk
+    k, first = _expand(-(-blocks.reshape(-1) // FDCT_BLOCKS))
+    tf = np.zeros((len(k), 4), np.int32)
+    tf[:, 0], tf[:, 1], tf[:, 2] = k // 3, k % 3, first * FDCT_BLOCKS
+    return desc, qtabs, int(per.sum()), tp, tf
+
+
+def forward_coefficients(images, shapes=None, quality=75, subsampling='420', qtables=None, device=None):
+    """Device half of the encode: uint8 images -> JpegCoefficients, libjpeg's quantised coefficients over the MCU-padded grid
+    (dummy blocks as libjpeg codes them), copied into pinned host memory on the current stream; no host synchronisation
+    (the result's wait() blocks until they have arrived; entropy_encode and decode_coefficients order themselves after it).
+
+    images: the packed 1-D uint8 RGB batch with shapes [(H, W)] (decode_jpeg_batch's output, augment_images' input); or
+    uint8 [H, W, 3] / [N, H, W, 3] RGB; or uint8 [H, W] / [N, H, W] grey (a one-component stream); or a list of [H, W, 3]
+    and [H, W] images of any sizes.  Tensors or arrays, on the host or the device.  A 3-D input whose last extent is 3 is
+    one RGB image.  quality 1 .. 100 (quant_tables) or qtables: 1 to 3 tables [64] in natural order, values 1 .. 255, for
+    luma, Cb and Cr (the last one given serves the remaining components).  subsampling '444' | '422' | '420' for RGB."""
+    tables = _tables(quality, qtables)
+    if device is not None:
+        dev = torch.device(device)
+    elif isinstance(images, torch.Tensor) and images.is_cuda:
+        dev = images.device
+    else:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    if dev.type != 'cuda':
+        raise ValueError('forward_coefficients runs on a GPU device, not %s' % dev)
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        flat, items = _encode_inputs(images, shapes, dev)
+        hdesc, qtabs, total, tp, tf = forward_plan(items, subsampling, tables)
+        desc, qt, a, b = _up(hdesc, dev), _up(qtabs.view(np.int16), dev), _up(tp, dev), _up(tf, dev)
+        coef = torch.empty(total, dtype=torch.int16, device=dev)
+        planes = torch.empty(total, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        check(lib().dbn_jpeg_forward(flat.data_ptr(), flat.numel(), desc.data_ptr(), qt.data_ptr(), len(items), a.data_ptr(), len(tp),
+                                     b.data_ptr(), len(tf), planes.data_ptr(), coef.data_ptr(), total, stream.cuda_stream), 'jpeg_forward')
+        host = torch.empty(total, dtype=torch.int16, pin_memory=True)
+        host.copy_(coef, non_blocking=True)
+        ready = torch.cuda.Event()
+        ready.record(stream)
+    hdesc[:, _D_OUT] = np.cumsum(hdesc[:, _D_W] * hdesc[:, _D_H] * 3) - hdesc[:, _D_W] * hdesc[:, _D_H] * 3  # as entropy_decode leaves it
+    obj = JpegCoefficients(host, hdesc, qtabs, np.zeros(len(items), np.int32))
+    obj.ready = ready
+    return obj
+
+
+def entropy_encode(obj, restart_interval=0, threads=MAX_THREADS, errors='raise'):
+    """Host half of the encode: JpegCoefficients -> list of JPEG byte strings (SOI, JFIF APP0, DQT, SOF0, DHT, DRI, SOS, one
+    interleaved scan with the Annex K Huffman tables, EOI), on min(len(obj), 16, threads) threads.  Coefficients are
+    taken as given, dummy blocks included: entropy_encode(entropy_decode(data), restart_interval=that stream's) reproduces
+    the scan bytes of a stream that uses the Annex K tables.  restart_interval: MCUs between RSTn markers, 0 .. 65535.
+    An image that cannot be coded raises JpegEncodeError(index, reason); errors='report': nothing raises; ->
+    (streams, errs) with streams[i] None and errs[i] the exception for such an image, which fails alone."""
+    if errors not in ('raise', 'report'):
+        raise ValueError("errors is 'raise' or 'report'")
+    if isinstance(restart_interval, bool) or int(restart_interval) != restart_interval or not 0 <= int(restart_interval) <= 65535:
+        raise ValueError('restart_interval must be an integer in 0 .. 65535, got %r' % (restart_interval, ))
+    ri, N = int(restart_interval), len(obj)
+    if N == 0:
+        raise ValueError('entropy_encode needs at least one image')
+    obj.wait()
+    coef = obj.coef.contiguous()
+    desc = np.ascontiguousarray(obj.desc, np.int64).copy()
+    desc[:, _D_STATUS] = np.asarray(obj.status)
+    qtabs = np.ascontiguousarray(obj.qtabs, np.uint16)
+    if coef.dtype != torch.int16 or coef.is_cuda or desc.shape != (N, _DESC) or qtabs.shape != (N, 3, 64):
+        raise ValueError('not the layout of JpegCoefficients')
+    L = lib()
+    per = np.zeros(N, np.int64)
+    total = int(L.dbn_jpeg_encode_bound(desc.ctypes.data, N, ri, per.ctypes.data))
+    if total < 0:
+        raise RuntimeError('libdbnet_hip: jpeg_encode_bound failed')
+    offs = np.zeros(N + 1, np.int64)
+    offs[1:] = np.cumsum(per)
+    out = np.empty(max(total, 1), np.uint8)  # the worst case; only the pages a stream reaches are ever touched
+    lens, status = np.zeros(N, np.int64), np.zeros(N, np.int32)
+    check(L.dbn_jpeg_encode_batch(coef.data_ptr(), coef.numel(), desc.ctypes.data, qtabs.ctypes.data, N, ri, out.ctypes.data, total,
+                                  offs.ctypes.data, lens.ctypes.data, status.ctypes.data, int(threads)), 'jpeg_encode_batch')
+    errs = [None if s == 0 else JpegEncodeError(i, ENCODE_REASONS.get(int(s), 'status %d' % s), int(s)) for i, s in enumerate(status)]
+    if errors == 'raise':
+        for e in errs:
+            if e is not None:
+                raise e
+    streams = [None if e is not None else out[o:o + n].tobytes() for o, n, e in zip(offs[:-1], lens, errs)]
+    return streams if errors == 'raise' else (streams, errs)
+
+
+def encode_jpeg_batch(images, shapes=None, quality=75, subsampling='420', qtables=None, restart_interval=0, threads=MAX_THREADS, device=None):
+    """uint8 images (the layouts of forward_coefficients) -> list of baseline JPEG byte strings.  The defaults are Pillow's /
+    imageio's (quality 75, 4:2:0, the Annex K Huffman tables): the file decodes to the pixels of the file the reference's
+    imageio.imwrite(path, img) writes."""
+    return entropy_encode(forward_coefficients(images, shapes, quality, subsampling, qtables, device), restart_interval, threads)
+
+
+def encode_jpeg(image, quality=75, subsampling='420', qtables=None, restart_interval=0, device=None):
+    """one uint8 [H, W, 3] (or grey [H, W]) image -> bytes"""
+    if getattr(image, 'ndim', 0) not in (2, 3) or (image.ndim == 3 and image.shape[2] != 3):
+        raise ValueError('encode_jpeg takes one uint8 [H, W, 3] or [H, W] image')
+    return encode_jpeg_batch([image], None, quality, subsampling, qtables, restart_interval, 1, device)[0]
+
+
+def save_jpegs(paths, images, shapes=None, **kw):
+    """encode_jpeg_batch(images, shapes, **kw) written to `paths`, one file per image: the reference's per-crop
+    word_<i>.jpg loop (test_ocr.py:176, utils.py:272) for crop_words' [M, 32, 100, 3] output in one call -> the paths"""
+    paths = [os.fspath(p) for p in paths]
+    datas = encode_jpeg_batch(images, shapes, **kw)
+    if len(paths) != len(datas):
+        raise ValueError('%d paths for %d images' % (len(paths), len(datas)))
+    for p, d in zip(paths, datas):
+        with open(p, 'wb') as f:
+            f.write(d)
+    return paths

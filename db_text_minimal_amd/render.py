@@ -304,9 +304,17 @@ def minmax_scale_u8(x):
 
 
 # ---- python -m db_text_minimal_amd.render: the shape of the reference's test.py ----------------------------------------
+def _is_jpeg(path):
+    return path.lower().endswith(('.jpg', '.jpeg'))
+
+
 def _read_image(path):
     if path.endswith('.npy'):
         img = np.load(path)
+    elif _is_jpeg(path):  # the project's own decoder; a kind it refuses (progressive, CMYK, ...) goes through PIL when that is installed
+        from .jpeg import decode_jpeg
+        with open(path, 'rb') as f:
+            return decode_jpeg(f.read(), fallback=True)
     else:
         from PIL import Image  # only when the suffix asks for it
         img = np.asarray(Image.open(path).convert('RGB'))
@@ -316,6 +324,13 @@ def _read_image(path):
 
 
 def _write_image(path, img):
+    """img: uint8 [H, W, 3] device tensor"""
+    if _is_jpeg(path):  # the project's own encoder (quality 75, 4:2:0: what Pillow writes by default); PIL is not imported
+        from .jpeg import encode_jpeg
+        with open(path, 'wb') as f:
+            f.write(encode_jpeg(img))
+        return
+    img = img.cpu().numpy()
     if path.endswith('.npy'):
         np.save(path, img)
     else:
@@ -330,18 +345,19 @@ def main(argv=None):
     from .models import DBTextModel
     from .postprocess import detect_boxes, detect_polygons
     ap = argparse.ArgumentParser(description='detect text in one image and draw the result (the reference\'s test.py)')
-    ap.add_argument('--image', required=True, help='.npy uint8 [H, W, 3], or an image file when PIL is installed')
+    ap.add_argument('--image', required=True, help='.npy uint8 [H, W, 3], a .jpg / .jpeg file, or another image file when PIL is installed')
     ap.add_argument('--model_path', required=True)
     ap.add_argument('--is_output_polygon', action='store_true')
     ap.add_argument('--heatmap', action='store_true', help='lay the probability map over the outlines (test.py)')
-    ap.add_argument('--out', default=None)
+    ap.add_argument('--out', default=None, help='.npy, .jpg / .jpeg (written by encode_jpeg), or another suffix when PIL is installed')
     ap.add_argument('--thresh', type=float, default=0.25)
     ap.add_argument('--box_thresh', type=float, default=0.5)
     ap.add_argument('--unclip_ratio', type=float, default=1.5)
     ap.add_argument('--alpha', type=float, default=0.6)
     args = ap.parse_args(argv)
     dev = torch.device('cuda')
-    img = torch.from_numpy(_read_image(args.image)).to(dev)
+    img = _read_image(args.image)
+    img = (img if isinstance(img, torch.Tensor) else torch.from_numpy(img)).to(dev)
     model = DBTextModel().to(dev)
     model.load_state_dict(torch.load(args.model_path, map_location=dev))
     model.eval()
@@ -353,7 +369,7 @@ def main(argv=None):
     res = detect(preds, args.thresh, args.box_thresh, unclip_ratio=args.unclip_ratio, dest_sizes=[tuple(img.shape[:2])])
     out = render_detections(img, preds, res, alpha=args.alpha, heatmap=args.heatmap)
     path = args.out or os.path.splitext(args.image)[0] + ('_poly' if args.is_output_polygon else '_rect') + '_result.npy'
-    _write_image(path, image_views(out, [tuple(img.shape[:2])])[0].cpu().numpy())
+    _write_image(path, image_views(out, [tuple(img.shape[:2])])[0])
     print(path)
 
 

@@ -852,6 +852,31 @@ int dbn_jpeg_entropy_batch(const unsigned char* blob, const long long* offs, int
 int dbn_jpeg_pixels(const short* coef, long coef_elems, const long long* desc, const unsigned short* qtabs, int N, const int* tab_idct,
                     int n_idct, const int* tab_rgb, int n_rgb, unsigned char* planes, unsigned char* out, long out_bytes, void* stream);
 
+/* ---- JPEG encode behind the device pipeline (csrc/jpeg_enc.hip): in the place of the reference's imageio / Pillow writes (utils.py:225,272,280,
+ * test_ocr.py:176,210, ts_request.py:38-39).  The decoder turned round: colour conversion, edge replication, chroma downsampling, libjpeg's
+ * slow-integer forward DCT and quantisation on the device, Huffman coding (Annex K tables) on the host; the coefficient layout, the descriptor
+ * and the tables of dbn_jpeg_entropy_batch are the hand-over.
+ * dbn_jpeg_forward: two launches on `stream`.  pixels: in_bytes bytes that hold every image; desc int64 [N][24] as above, field 4 being the byte
+ * offset of the image's first pixel in `pixels` (any alignment) and `components` 1 for uint8 [H][W] grey, 3 for uint8 [H][W][3] RGB; sampling
+ * 1x1, 2x1 or 2x2 luma with 1x1 chroma, and the grids the size and the sampling give; qtabs uint16 [N][3][64] natural order (entries 1 .. 255).
+ * tab_planes int32 [n_planes][4] = {image, chunk of 256 cells, 0, 0} over the image's 8 * MCU columns x 8 * MCU rows cells (a cell: hmax x vmax
+ * pixels); tab_fdct int32 [n_fdct][4] = {image, component, first block, 0}, one entry per 32 blocks of the padded grid; planes: coef_elems bytes
+ * of workspace, 8-byte aligned; coef (coef_elems int16) and qtabs 16-byte aligned.  Every block of the padded grid is written: a dummy block has
+ * zero AC and the DC of the previous block in MCU order, as libjpeg codes it.  Entries that would leave a buffer are skipped.
+ * dbn_jpeg_encode_bound: per_image[n] (may be NULL) and the returned sum: bytes a stream can need at most (header, 416 per block, 4 per
+ * restart); 0 for a descriptor that cannot be encoded, -1 for bad arguments.  restart_interval: MCUs, 0 .. 65535.
+ * dbn_jpeg_encode_batch: host; codes N images on min(N, 16, threads) threads.  Image n's stream (SOI, JFIF APP0, DQT, SOF0, DHT, DRI, SOS, one
+ * interleaved scan, EOI) goes to out[offs[n] .. offs[n + 1]) (offs int64 [N + 1] ascending, offs[N] <= out_bytes), its length to lens[n]; no
+ * byte outside an image's slot is written.  status[n]: 0 coded, 1 the descriptor's own status is not 0, 2 bad descriptor, 3 a quantisation
+ * value outside 1 .. 255, 4 a DC difference of more than 11 bits, 5 an AC coefficient of more than 10 bits, 6 the slot is too small.  An image
+ * that is not coded has length 0 and fails alone.  Coefficients are taken as given, dummy blocks included. */
+int dbn_jpeg_forward(const unsigned char* pixels, long in_bytes, const long long* desc, const unsigned short* qtabs, int N,
+                     const int* tab_planes, int n_planes, const int* tab_fdct, int n_fdct, unsigned char* planes, short* coef, long coef_elems,
+                     void* stream);
+long dbn_jpeg_encode_bound(const long long* desc, int N, int restart_interval, long long* per_image);
+int dbn_jpeg_encode_batch(const short* coef, long coef_elems, const long long* desc, const unsigned short* qtabs, int N, int restart_interval,
+                          unsigned char* out, long out_bytes, const long long* offs, long long* lens, int* status, int threads);
+
 #ifdef __cplusplus
 }
 #endif
