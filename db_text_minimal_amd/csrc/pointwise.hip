@@ -283,10 +283,19 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_wide_kernel(const float* 
     c2[c] = (float)(s2 / M);
 }
 
+// the value a store in the storage type leaves in memory (round to nearest even), as fp32
+template <int AT>
+__device__ __forceinline__ float round_to_storage(float v) {
+    if constexpr (AT == 1) return (float)(__bf16)v;
+    else if constexpr (AT == 2) return (float)(_Float16)v;
+    else return v;
+}
+
 // dy = gamma*rstd*(g - c1 - xhat*c2); optionally also emits g (the ReLU-masked dout).
 // bias_part (optional, needs 256 % (C/4) == 0): per-block column sums of dy, [C][gridDim.x] — the gradient of the bias of the
 // conv that feeds this BatchNorm (analytically zero; the reference's value is the round-off of exactly this sum), so that no
-// separate pass re-reads dy for it.
+// separate pass re-reads dy for it.  The sum is over dy AS STORED (rounded to the storage type), which is what a dbn_col_sum_t
+// pass over dy — and the convolution's own backward — reads.
 template <int AT, int QW>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const void* __restrict__ y, const void* __restrict__ zmask,
                                                            const float* __restrict__ msc, const float* __restrict__ msh,
@@ -339,6 +348,16 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const void* __restric
             }
             const f32x4 xh = (v[q] - mu[q]) * rs[q];
             d[q] = gr[q] * (g[q] - k1[q] - xh * k2[q]);
+            // rounded to the storage type ONCE, here: the store below converts this value exactly, and the bias sum reads the same
+            // bits.  The empty asm keeps the conversion apart from the product: fused with it (v_fma_mixlo_f16) the product is
+            // rounded to fp16 once, while a second conversion of the same expression, left as v_cvt_pk_f16_f32, rounds the fp32
+            // product again — the two then differ by one fp16 ulp in about one element of 2^13, and the sum no longer is that of dy.
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float t = d[q][e];
+                asm("" : "+v"(t));
+                d[q][e] = round_to_storage<AT>(t);
+            }
             bsum[q] += d[q];
             go[q] = acc ? g[q] + old[q] : g[q];
         }
@@ -481,12 +500,6 @@ __global__ void bnrelu_maxpool_fwd_kernel(const void* __restrict__ y, const floa
 
 // dz[n,ih,iw,c] = [z>0] * sum over windows containing (ih,iw) whose max equals z of dpool
 // 16-bit storage: the pooled value is the ROUNDED maximum, so equality is tested on the rounded activation
-template <int AT>
-__device__ __forceinline__ float round_to_storage(float v) {
-    if constexpr (AT == 1) return (float)(__bf16)v;
-    else if constexpr (AT == 2) return (float)(_Float16)v;
-    else return v;
-}
 // bn_part (optional, needs 256 % (C/4) == 0 so that a thread keeps its channel quad): per-block partial sums of the two
 // reductions of the BatchNorm backward that consumes dz — sum(dz) and sum(dz * xhat) per channel, [2*C][gridDim.x] — so that
 // the stem's BatchNorm backward does not re-read y and dz (2 x 420 MB at bs16) to form them.

@@ -104,3 +104,64 @@ def report_robust(tag, got, ref, atol, rtol, frac=0.999):
     f = float(ok.double().mean())
     print('%s: %.5f of elements within tol, mean abs err %.3e' % (tag, f, float((got - ref).abs().mean())))
     assert f >= frac, tag
+
+
+# ---- float64 pins of the storage-typed kernels (test_train16_ops_gpu.py, test_bn_pool_ops_gpu.py) ----
+U = 2.0**-24
+DT = {0: torch.float32, 1: torch.bfloat16, 2: torch.float16}
+SR = {0: 2.0**-24, 1: 2.0**-8, 2: 2.0**-11}  # unit roundoff of the storage type (round to nearest even)
+ETA = {0: 0.0, 1: 0.0, 2: 2.0**-25}  # absolute floor of one rounding: half the fp16 subnormal spacing
+NAN = float('nan')
+
+
+def gen(seed, dev=DEV):
+    return torch.Generator(device=dev).manual_seed(seed)
+
+
+CHUNK = 1 << 24  # elements per comparison slice (keeps the float64 temporaries of the step-sized checks small)
+
+
+def within(tag, got, ref, bound):
+    """|got - ref| <= bound elementwise; got must be finite everywhere (NaN-filled outputs that were never written fail here)."""
+    got, ref = got.detach().reshape(-1), ref.detach().reshape(-1)
+    bound = torch.as_tensor(bound, dtype=torch.float64).detach().reshape(-1)
+    assert got.numel() == ref.numel() and bound.numel() in (1, ref.numel()), (tag, got.shape, ref.shape, bound.shape)
+    worst, emax, nover, first = 0.0, 0.0, 0, None
+    for i in range(0, got.numel(), CHUNK):
+        g = got[i:i + CHUNK].double()
+        r = ref[i:i + CHUNK].to(g.device, torch.float64)
+        b = (bound if bound.numel() == 1 else bound[i:i + CHUNK]).to(g.device, torch.float64)
+        nf = ~torch.isfinite(g)
+        assert not bool(nf.any()), '%s: %d non-finite elements, the first at %d' % (tag, int(nf.sum()), i + int(nf.nonzero()[0]))
+        err = (g - r).abs()
+        over = err > b
+        emax = max(emax, float(err.max()))
+        worst = max(worst, float(torch.where(err > 0, err / b.clamp_min(1e-300), torch.zeros_like(err)).max()))
+        if bool(over.any()):
+            nover += int(over.sum())
+            if first is None:
+                j = int(over.nonzero()[0])
+                first = (i + j, float(g[j]), float(r[j]), float(b[j] if b.numel() > 1 else b[0]))
+    msg = '%s: max err %.3e, worst err / bound %.3f' % (tag, emax, worst)
+    print(msg)
+    assert nover == 0, msg + ' (%d elements over; the first at %d: got %r ref %r bound %.3e)' % ((nover, ) + first)
+
+
+def exact(tag, got, ref):
+    """got == ref exactly (as numbers: -0 == +0), got finite everywhere."""
+    got, ref = got.detach().reshape(-1), ref.detach().reshape(-1)
+    assert got.numel() == ref.numel(), (tag, got.shape, ref.shape)
+    nne, first = 0, None
+    for i in range(0, got.numel(), CHUNK):
+        g = got[i:i + CHUNK].double()
+        r = ref[i:i + CHUNK].to(g.device, torch.float64)
+        nf = ~torch.isfinite(g)
+        assert not bool(nf.any()), '%s: %d non-finite elements, the first at %d' % (tag, int(nf.sum()), i + int(nf.nonzero()[0]))
+        ne = g != r
+        if bool(ne.any()):
+            nne += int(ne.sum())
+            if first is None:
+                j = int(ne.nonzero()[0])
+                first = (i + j, float(g[j]), float(r[j]))
+    assert nne == 0, '%s: %d of %d elements differ; the first at %d: got %r ref %r' % ((tag, nne, got.numel()) + first)
+    print('%s: %d elements bit-exact' % (tag, got.numel()))
