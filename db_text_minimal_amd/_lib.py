@@ -59,6 +59,14 @@ SIGNATURES = {
     'dbn_jpeg_forward': 'plppipipipplp',
     'dbn_jpeg_encode_bound': 'piip',
     'dbn_jpeg_encode_batch': 'plppiiplpppi',
+    'dbn_jpeg_optimal_table': 'pppp',
+    'dbn_jpeg_encode_batch_opt': 'plppiiplpppii',
+    'dbn_jpeg_huff_plan': 'ppilipppp',
+    'dbn_jpeg_huff_hist': 'plpiplippp',
+    'dbn_jpeg_huff_annex_k': 'pp',
+    'dbn_jpeg_huff_tables': 'ppipppi',
+    'dbn_jpeg_huff_code': 'plpippllipiplplpp',
+    'dbn_jpeg_huff_headers': 'ppiipippp',
     'dbn_detect_poly_ws_bytes': 'iiii',
     'dbn_detect_poly_verts_cap': 'iii',
     'dbn_detect_poly': 'piiiifi' + 'pppppp',

@@ -8,7 +8,8 @@
 //                                    MCU-padded grid -> int16 coefficients, 64 per block in NATURAL order).  Mixed sizes and
 //                                    samplings run in one call: each workgroup looks its work up in a host-built table.
 //   host    dbn_jpeg_encode_bound    bytes a batch's streams can need at most (per image and in total)
-//           dbn_jpeg_encode_batch    Huffman-codes N images (Annex K tables) on up to min(N, 16, threads) threads, each
+//           dbn_jpeg_optimal_table   libjpeg's optimised Huffman table for 256 symbol counts
+//           dbn_jpeg_encode_batch    (_opt: with each image's own optimised tables) Huffman-codes N images (Annex K tables) on up to min(N, 16, threads) threads, each
 //                                    into its own slot of one output buffer: SOI, JFIF APP0, DQT, SOF0, DHT, DRI, SOS, one
 //                                    interleaved scan, EOI.  Coefficients are taken as given, dummy blocks included, so
 //                                    decoding a stream and encoding the result reproduces its scan bytes.
@@ -24,11 +25,11 @@
 #include <vector>
 
 #include "common.h"
+#include "jpeg_enc.h"
+
+using namespace dbn_jpeg;
 
 namespace {
-
-constexpr int JP_DESC = 24;  // int64 per image, see include/dbnet_hip.h
-enum { D_COEF = 0, D_W, D_H, D_NC, D_OUT, D_QT, D_COMP /* 4 per component: bw, bh, h, v */, D_HMAX = 18, D_VMAX, D_MCUX, D_MCUY, D_STATUS, D_RI };
 
 const unsigned char kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                                    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
@@ -247,8 +248,6 @@ __global__ void __launch_bounds__(FD_THREADS) jpeg_fdct_kernel(const unsigned ch
 }
 
 // ---- host: the Huffman stage --------------------------------------------------------------------------------------------
-enum { ES_OK = 0, ES_NO_IMAGE, ES_BAD_DESC, ES_TABLE, ES_DC_RANGE, ES_AC_RANGE, ES_NO_ROOM };
-
 // Annex K.3: counts per code length 1 .. 16, then the values
 const unsigned char kDcLumaBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
 const unsigned char kDcChromaBits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
@@ -274,60 +273,27 @@ const unsigned char kAcChromaVals[162] = {
     0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
     0xfa};
 
-struct Codes {
-    unsigned short code[256];
-    unsigned char size[256];  // 0: no code for this symbol
-    Codes(const unsigned char* bits, const unsigned char* vals) {
-        memset(code, 0, sizeof(code));
-        memset(size, 0, sizeof(size));
-        int c = 0, k = 0;
-        for (int l = 1; l <= 16; ++l) {
-            for (int i = 0; i < bits[l - 1]; ++i, ++k, ++c) code[vals[k]] = (unsigned short)c, size[vals[k]] = (unsigned char)l;
-            c <<= 1;
-        }
-    }
-};
+
+HuffSpec make_spec(const unsigned char* bits, const unsigned char* vals, int nvals) {
+    HuffSpec s;
+    memset(&s, 0, sizeof(s));
+    memcpy(s.bits, bits, 16);
+    memcpy(s.vals, vals, nvals);
+    s.nvals = nvals;
+    return s;
+}
 
 struct Tables {
-    Codes dc[2], ac[2];
-    Tables() : dc{Codes(kDcLumaBits, kDcVals), Codes(kDcChromaBits, kDcVals)}, ac{Codes(kAcLumaBits, kAcLumaVals), Codes(kAcChromaBits, kAcChromaVals)} {}
+    Codes t[4];  // DC 0, AC 0, DC 1, AC 1
+    explicit Tables(const HuffSpec* s) {
+        for (int i = 0; i < 4; ++i) t[i] = Codes(s[i].bits, s[i].vals);
+    }
 };
 
 const Tables& tables() {
-    static const Tables t;
+    static const Tables t(annex_k());
     return t;
 }
-
-// what the host stage needs of a descriptor, checked: grids that the size and the sampling give, coefficients inside the buffer
-struct Geo {
-    int W, H, nc, mcux, mcuy, h[3], v[3], bw[3], bh[3];
-    long coef, qt, comp_off[3], blocks;
-};
-
-int load_geo(const long long* d, long coef_elems, long qt_elems, Geo& g) {
-    if (d[D_STATUS] != 0) return ES_NO_IMAGE;
-    const long long W = d[D_W], H = d[D_H], nc = d[D_NC];
-    if (W < 1 || H < 1 || W > 65535 || H > 65535 || (nc != 1 && nc != 3)) return ES_BAD_DESC;
-    g.W = (int)W, g.H = (int)H, g.nc = (int)nc, g.coef = (long)d[D_COEF], g.qt = (long)d[D_QT];
-    const long long h0 = d[D_COMP + 2], v0 = d[D_COMP + 3];
-    if (!((h0 == 1 && v0 == 1) || (nc == 3 && h0 == 2 && (v0 == 1 || v0 == 2)))) return ES_BAD_DESC;
-    g.mcux = (int)((W + 8 * h0 - 1) / (8 * h0)), g.mcuy = (int)((H + 8 * v0 - 1) / (8 * v0));
-    g.blocks = 0;
-    for (int c = 0; c < (int)nc; ++c) {
-        g.h[c] = c == 0 ? (int)h0 : 1, g.v[c] = c == 0 ? (int)v0 : 1;
-        g.bw[c] = g.mcux * g.h[c], g.bh[c] = g.mcuy * g.v[c];
-        if (d[D_COMP + 4 * c] != g.bw[c] || d[D_COMP + 4 * c + 1] != g.bh[c] || d[D_COMP + 4 * c + 2] != g.h[c] || d[D_COMP + 4 * c + 3] != g.v[c])
-            return ES_BAD_DESC;
-        g.comp_off[c] = g.blocks * 64;
-        g.blocks += (long)g.bw[c] * g.bh[c];
-    }
-    if (g.coef < 0 || g.coef + g.blocks * 64 > coef_elems || g.qt < 0 || g.qt + nc * 64 > qt_elems) return ES_BAD_DESC;
-    return ES_OK;
-}
-
-constexpr long kHeaderBytes = 704;  // SOI 2, APP0 18, 3 DQT 207, SOF0 19, 4 DHT 432, DRI 6, SOS 14, EOI 2
-// A block takes at most 9 + 11 bits of DC and 63 x (16 + 10) bits of AC: 208 bytes, every one of which may be FF and stuffed.
-constexpr long kBlockBytes = 416;
 
 long image_bound(const Geo& g, int ri) {
     const long mcus = (long)g.mcux * g.mcuy;
@@ -366,20 +332,15 @@ inline int nbits(int v) {
     return v ? 32 - __builtin_clz((unsigned)v) : 0;
 }
 
-void put_dht(Put& w, int tc_th, const unsigned char* bits, const unsigned char* vals, int nvals) {
-    w.be16(0xFFC4), w.be16(2 + 1 + 16 + nvals), w.byte(tc_th);
-    for (int i = 0; i < 16; ++i) w.byte(bits[i]);
-    for (int i = 0; i < nvals; ++i) w.byte(vals[i]);
+void put_dht(Put& w, int tc_th, const HuffSpec& s) {
+    w.be16(0xFFC4), w.be16(2 + 1 + 16 + s.nvals), w.byte(tc_th);
+    for (int i = 0; i < 16; ++i) w.byte(s.bits[i]);
+    for (int i = 0; i < s.nvals; ++i) w.byte(s.vals[i]);
 }
 
-// one stream into [out, out + room): a status and the stream's length
-int encode_image(const short* coef, const unsigned short* qtabs, const Geo& g, int ri, unsigned char* out, long room, long long* len) {
-    const unsigned short* q = qtabs + g.qt;
-    for (int i = 0; i < 64 * g.nc; ++i)
-        if (q[i] < 1 || q[i] > 255) return ES_TABLE;
+void put_header(Put& w, const unsigned short* q, const Geo& g, int ri, const HuffSpec* specs) {
     int tq[3] = {0, 1, 1};
     if (g.nc == 3 && memcmp(q + 64, q + 128, 64 * sizeof(unsigned short)) != 0) tq[2] = 2;
-    Put w{out, out + room};
     w.be16(0xFFD8);
     w.be16(0xFFE0), w.be16(16);
     const unsigned char jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
@@ -391,26 +352,30 @@ int encode_image(const short* coef, const unsigned short* qtabs, const Geo& g, i
     }
     w.be16(0xFFC0), w.be16(8 + 3 * g.nc), w.byte(8), w.be16(g.H), w.be16(g.W), w.byte(g.nc);
     for (int c = 0; c < g.nc; ++c) w.byte(c + 1), w.byte(g.h[c] << 4 | g.v[c]), w.byte(tq[c]);
-    put_dht(w, 0x00, kDcLumaBits, kDcVals, 12);
-    put_dht(w, 0x10, kAcLumaBits, kAcLumaVals, 162);
+    put_dht(w, 0x00, specs[0]);
+    put_dht(w, 0x10, specs[1]);
     if (g.nc == 3) {
-        put_dht(w, 0x01, kDcChromaBits, kDcVals, 12);
-        put_dht(w, 0x11, kAcChromaBits, kAcChromaVals, 162);
+        put_dht(w, 0x01, specs[2]);
+        put_dht(w, 0x11, specs[3]);
     }
     if (ri > 0) w.be16(0xFFDD), w.be16(4), w.be16(ri);
     w.be16(0xFFDA), w.be16(6 + 2 * g.nc), w.byte(g.nc);
     for (int c = 0; c < g.nc; ++c) w.byte(c + 1), w.byte(c == 0 ? 0x00 : 0x11);
     w.byte(0), w.byte(63), w.byte(0);
+}
 
-    const Tables& T = tables();
+// The scan of one image, block after block in MCU order with the DC predictors reset at every restart interval, handed to
+// `sink`: restart(k) before interval k > 0, then per block dc(table, category, extra bits) and ac(table, run << 4 | size,
+// size, extra bits).  The gather pass of optimize and the coding pass walk the same way; a status other than ES_OK ends it.
+template <typename Sink>
+int walk_scan(const short* coef, const Geo& g, int ri, Sink& sink) {
     int pred[3] = {0, 0, 0};
     const long mcus = (long)g.mcux * g.mcuy;
     long to_restart = ri;
     int next_rst = 0;
     for (long mcu = 0; mcu < mcus; ++mcu) {
         if (ri > 0 && mcu && to_restart == 0) {
-            w.flush();
-            w.be16(0xFFD0 + next_rst);
+            sink.restart(next_rst);
             next_rst = (next_rst + 1) & 7;
             pred[0] = pred[1] = pred[2] = 0;
             to_restart = ri;
@@ -418,8 +383,7 @@ int encode_image(const short* coef, const unsigned short* qtabs, const Geo& g, i
         --to_restart;
         const long my = mcu / g.mcux, mx = mcu - my * g.mcux;
         for (int c = 0; c < g.nc; ++c) {
-            const Codes& dc = T.dc[c ? 1 : 0];
-            const Codes& ac = T.ac[c ? 1 : 0];
+            const int t = c ? 1 : 0;
             for (int v = 0; v < g.v[c]; ++v)
                 for (int u = 0; u < g.h[c]; ++u) {
                     const short* k64 = coef + g.coef + g.comp_off[c] + ((my * g.v[c] + v) * g.bw[c] + mx * g.h[c] + u) * 64;
@@ -427,8 +391,7 @@ int encode_image(const short* coef, const unsigned short* qtabs, const Geo& g, i
                     pred[c] = k64[0];
                     int s = nbits(d);
                     if (s > 11) return ES_DC_RANGE;
-                    w.bits(dc.code[s], dc.size[s]);
-                    if (s) w.bits((unsigned)(d < 0 ? d - 1 : d) & ((1u << s) - 1), s);
+                    sink.dc(t, s, (unsigned)(d < 0 ? d - 1 : d) & ((1u << s) - 1));
                     int run = 0;
                     for (int k = 1; k < 64; ++k) {
                         const int x = k64[kZigzag[k]];
@@ -437,21 +400,70 @@ int encode_image(const short* coef, const unsigned short* qtabs, const Geo& g, i
                             continue;
                         }
                         while (run > 15) {
-                            w.bits(ac.code[0xF0], ac.size[0xF0]);
+                            sink.ac(t, 0xF0, 0, 0);
                             run -= 16;
                         }
                         s = nbits(x);
                         if (s > 10) return ES_AC_RANGE;
-                        const int rs = run << 4 | s;
-                        w.bits(ac.code[rs], ac.size[rs]);
-                        w.bits((unsigned)(x < 0 ? x - 1 : x) & ((1u << s) - 1), s);
+                        sink.ac(t, run << 4 | s, s, (unsigned)(x < 0 ? x - 1 : x) & ((1u << s) - 1));
                         run = 0;
                     }
-                    if (run) w.bits(ac.code[0], ac.size[0]);
+                    if (run) sink.ac(t, 0, 0, 0);
                 }
         }
-        if (w.over) return ES_NO_ROOM;
+        if (sink.mcu_done()) return ES_NO_ROOM;
     }
+    return ES_OK;
+}
+
+struct CountSink {
+    long long freq[4][256];
+    CountSink() { memset(freq, 0, sizeof(freq)); }
+    inline void restart(int) {}
+    inline void dc(int t, int s, unsigned) { ++freq[2 * t][s]; }
+    inline void ac(int t, int rs, int, unsigned) { ++freq[2 * t + 1][rs]; }
+    inline bool mcu_done() { return false; }
+};
+
+struct CodeSink {
+    Put& w;
+    const Codes* T;
+    inline void restart(int k) {
+        w.flush();
+        w.be16(0xFFD0 + k);
+    }
+    inline void dc(int t, int s, unsigned extra) {
+        w.bits(T[2 * t].code[s], T[2 * t].size[s]);
+        if (s) w.bits(extra, s);
+    }
+    inline void ac(int t, int rs, int s, unsigned extra) {
+        w.bits(T[2 * t + 1].code[rs], T[2 * t + 1].size[rs]);
+        if (s) w.bits(extra, s);
+    }
+    inline bool mcu_done() { return w.over; }
+};
+
+// one stream into [out, out + room): a status and the stream's length.  optimize: a gather pass over the scan first, and
+// the image's own tables (libjpeg's jpeg_gen_optimal_table) in its DHT segments and its scan.
+int encode_image(const short* coef, const unsigned short* qtabs, const Geo& g, int ri, unsigned char* out, long room, long long* len, bool optimize) {
+    int s = check_qtabs(qtabs, g);
+    if (s != ES_OK) return s;
+    HuffSpec own[4];
+    Tables* mine = nullptr;
+    if (optimize) {
+        CountSink cs;
+        if ((s = walk_scan(coef, g, ri, cs)) != ES_OK) return s;
+        for (int t = 0; t < (g.nc == 3 ? 4 : 2); ++t)
+            if ((s = optimal_table(cs.freq[t], own[t])) != ES_OK) return s;
+        if (g.nc != 3) own[2] = own[0], own[3] = own[1];
+        mine = new Tables(own);
+    }
+    Put w{out, out + room};
+    put_header(w, qtabs + g.qt, g, ri, optimize ? own : annex_k());
+    CodeSink code{w, optimize ? mine->t : tables().t};
+    s = walk_scan(coef, g, ri, code);
+    delete mine;
+    if (s != ES_OK) return s;
     w.flush();
     w.be16(0xFFD9);
     if (w.over) return ES_NO_ROOM;
@@ -461,8 +473,112 @@ int encode_image(const short* coef, const unsigned short* qtabs, const Geo& g, i
 
 }  // namespace
 
-extern "C" {
+namespace dbn_jpeg {
 
+Codes::Codes(const unsigned char* bits, const unsigned char* vals) {
+    memset(code, 0, sizeof(code));
+    memset(size, 0, sizeof(size));
+    int c = 0, k = 0;
+    for (int l = 1; l <= 16; ++l) {
+        for (int i = 0; i < bits[l - 1]; ++i, ++k, ++c) code[vals[k]] = (unsigned short)c, size[vals[k]] = (unsigned char)l;
+        c <<= 1;
+    }
+}
+
+const HuffSpec* annex_k() {
+    static const HuffSpec s[4] = {make_spec(kDcLumaBits, kDcVals, 12), make_spec(kAcLumaBits, kAcLumaVals, 162),
+                                  make_spec(kDcChromaBits, kDcVals, 12), make_spec(kAcChromaBits, kAcChromaVals, 162)};
+    return s;
+}
+
+int load_geo(const long long* d, long coef_elems, long qt_elems, Geo& g) {
+    if (d[D_STATUS] != 0) return ES_NO_IMAGE;
+    const long long W = d[D_W], H = d[D_H], nc = d[D_NC];
+    if (W < 1 || H < 1 || W > 65535 || H > 65535 || (nc != 1 && nc != 3)) return ES_BAD_DESC;
+    g.W = (int)W, g.H = (int)H, g.nc = (int)nc, g.coef = (long)d[D_COEF], g.qt = (long)d[D_QT];
+    const long long h0 = d[D_COMP + 2], v0 = d[D_COMP + 3];
+    if (!((h0 == 1 && v0 == 1) || (nc == 3 && h0 == 2 && (v0 == 1 || v0 == 2)))) return ES_BAD_DESC;
+    g.mcux = (int)((W + 8 * h0 - 1) / (8 * h0)), g.mcuy = (int)((H + 8 * v0 - 1) / (8 * v0));
+    g.blocks = 0;
+    for (int c = 0; c < (int)nc; ++c) {
+        g.h[c] = c == 0 ? (int)h0 : 1, g.v[c] = c == 0 ? (int)v0 : 1;
+        g.bw[c] = g.mcux * g.h[c], g.bh[c] = g.mcuy * g.v[c];
+        if (d[D_COMP + 4 * c] != g.bw[c] || d[D_COMP + 4 * c + 1] != g.bh[c] || d[D_COMP + 4 * c + 2] != g.h[c] || d[D_COMP + 4 * c + 3] != g.v[c])
+            return ES_BAD_DESC;
+        g.comp_off[c] = g.blocks * 64;
+        g.blocks += (long)g.bw[c] * g.bh[c];
+    }
+    if (g.coef < 0 || g.coef + g.blocks * 64 > coef_elems || g.qt < 0 || g.qt + nc * 64 > qt_elems) return ES_BAD_DESC;
+    return ES_OK;
+}
+
+int check_qtabs(const unsigned short* qtabs, const Geo& g) {
+    const unsigned short* q = qtabs + g.qt;
+    for (int i = 0; i < 64 * g.nc; ++i)
+        if (q[i] < 1 || q[i] > 255) return ES_TABLE;
+    return ES_OK;
+}
+
+long write_header(const unsigned short* qtabs, const Geo& g, int ri, const HuffSpec* specs, unsigned char* out, long room) {
+    Put w{out, out + room};
+    put_header(w, qtabs + g.qt, g, ri, specs);
+    return w.over ? -1 : (long)(w.p - out);
+}
+
+// jchuff.c jpeg_gen_optimal_table: a pseudo-symbol 256 of count 1 keeps the all-ones code unused; the two least counts are
+// merged until one tree is left, a tie going to the larger symbol; code lengths above 16 are shortened by moving pairs of
+// symbols up (the bits[] adjustment of section K.2); the pseudo-symbol's place, the longest code, is dropped; symbols are
+// listed by length, then by value.  A DC table has at most 12 symbols and an AC table at most 162 (runs 0 .. 15 with sizes
+// 1 .. 10, EOB and ZRL), so four such DHT segments are never longer than the Annex K ones kHeaderBytes counts.
+int optimal_table(const long long* freq_in, HuffSpec& out) {
+    constexpr int MAX_CLEN = 32;
+    long long freq[257];
+    int bits[MAX_CLEN + 1] = {0}, codesize[257] = {0}, others[257];
+    for (int i = 0; i < 256; ++i) freq[i] = freq_in[i] > 0 ? freq_in[i] : 0;
+    freq[256] = 1;
+    for (int i = 0; i < 257; ++i) others[i] = -1;
+    for (;;) {
+        int c1 = -1, c2 = -1;
+        long long v = 0x7fffffffffffffffLL;
+        for (int i = 0; i <= 256; ++i)
+            if (freq[i] && freq[i] <= v) v = freq[i], c1 = i;
+        v = 0x7fffffffffffffffLL;
+        for (int i = 0; i <= 256; ++i)
+            if (freq[i] && freq[i] <= v && i != c1) v = freq[i], c2 = i;
+        if (c2 < 0) break;
+        freq[c1] += freq[c2];
+        freq[c2] = 0;
+        for (++codesize[c1]; others[c1] >= 0;) c1 = others[c1], ++codesize[c1];
+        others[c1] = c2;
+        for (++codesize[c2]; others[c2] >= 0;) c2 = others[c2], ++codesize[c2];
+    }
+    for (int i = 0; i <= 256; ++i)
+        if (codesize[i]) {
+            if (codesize[i] > MAX_CLEN) return ES_CODE_LENGTH;
+            ++bits[codesize[i]];
+        }
+    int i;
+    for (i = MAX_CLEN; i > 16; --i)
+        while (bits[i] > 0) {
+            int j = i - 2;
+            while (bits[j] == 0) --j;
+            bits[i] -= 2, ++bits[i - 1], bits[j + 1] += 2, --bits[j];
+        }
+    while (bits[i] == 0) --i;
+    --bits[i];
+    memset(&out, 0, sizeof(out));
+    for (int l = 1; l <= 16; ++l) out.bits[l - 1] = (unsigned char)bits[l];
+    int p = 0;
+    for (int l = 1; l <= MAX_CLEN; ++l)
+        for (int j = 0; j < 256; ++j)
+            if (codesize[j] == l) out.vals[p++] = (unsigned char)j;
+    out.nvals = p;
+    return ES_OK;
+}
+
+}  // namespace dbn_jpeg
+
+extern "C" {
 // pixels: in_bytes bytes holding every image; desc int64 [N][24] as dbn_jpeg_entropy_batch writes it, with field 4 the byte
 // offset of the image's first pixel in `pixels` (any alignment) and `components` 1 for uint8 [H][W] grey, 3 for uint8
 // [H][W][3] RGB; qtabs uint16 [N][3][64] natural order; tab_planes int32 [n_planes][4] = {image, chunk of 256 cells, 0, 0} over
@@ -498,13 +614,33 @@ long dbn_jpeg_encode_bound(const long long* desc, int N, int restart_interval, l
     return total;
 }
 
+// freq int64 [256] -> bits uint8 [16] (symbols per code length 1 .. 16), vals uint8 [256] and *nvals: the table libjpeg's
+// jpeg_gen_optimal_table makes of these counts (what Pillow's optimize=True writes).  1: no count is positive, a count is
+// negative, or libjpeg itself gives up (a code of more than 32 bits).
+int dbn_jpeg_optimal_table(const long long* freq, unsigned char* bits, unsigned char* vals, int* nvals) {
+    DBN_REQUIRE(freq && bits && vals && nvals);
+    bool any = false;
+    for (int i = 0; i < 256; ++i) {
+        DBN_REQUIRE(freq[i] >= 0);
+        any = any || freq[i] > 0;
+    }
+    DBN_REQUIRE(any);
+    HuffSpec s;
+    DBN_REQUIRE(optimal_table(freq, s) == ES_OK);
+    memcpy(bits, s.bits, 16);
+    memcpy(vals, s.vals, 256);
+    *nvals = s.nvals;
+    return DBN_OK;
+}
+
 // coef / desc / qtabs: the layout of dbn_jpeg_entropy_batch, on the host.  Image n's stream goes to out[offs[n] .. offs[n + 1])
 // (offs int64 [N + 1], ascending, offs[N] <= out_bytes) and lens[n] receives its length; no byte outside an image's slot is
 // written.  status[n]: 0 coded, 1 the descriptor's own status is not 0, 2 bad descriptor, 3 a quantisation value outside
-// 1 .. 255, 4 a DC difference of more than 11 bits, 5 an AC coefficient of more than 10 bits, 6 the slot is too small; an
-// image that is not coded has length 0 and fails alone.
-int dbn_jpeg_encode_batch(const short* coef, long coef_elems, const long long* desc, const unsigned short* qtabs, int N, int restart_interval,
-                          unsigned char* out, long out_bytes, const long long* offs, long long* lens, int* status, int threads) {
+// 1 .. 255, 4 a DC difference of more than 11 bits, 5 an AC coefficient of more than 10 bits, 6 the slot is too small, 7
+// (optimize only) libjpeg's table builder gives up; an image that is not coded has length 0 and fails alone.  optimize: each
+// image's own Huffman tables, as libjpeg's optimize_coding makes them, in place of the Annex K ones.
+int dbn_jpeg_encode_batch_opt(const short* coef, long coef_elems, const long long* desc, const unsigned short* qtabs, int N, int restart_interval,
+                              unsigned char* out, long out_bytes, const long long* offs, long long* lens, int* status, int threads, int optimize) {
     DBN_REQUIRE(coef && desc && qtabs && out && offs && lens && status && N > 0 && coef_elems >= 0 && out_bytes >= 0);
     DBN_REQUIRE(restart_interval >= 0 && restart_interval <= 65535 && offs[0] >= 0 && offs[N] <= out_bytes);
     for (int n = 0; n < N; ++n) DBN_REQUIRE(offs[n + 1] >= offs[n]);
@@ -520,7 +656,8 @@ int dbn_jpeg_encode_batch(const short* coef, long coef_elems, const long long* d
             Geo g;
             lens[n] = 0;
             int s = load_geo(desc + (long)n * JP_DESC, coef_elems, qt_elems, g);
-            if (s == ES_OK) s = encode_image(coef, qtabs, g, restart_interval, out + offs[n], (long)(offs[n + 1] - offs[n]), lens + n);
+            if (s == ES_OK)
+                s = encode_image(coef, qtabs, g, restart_interval, out + offs[n], (long)(offs[n + 1] - offs[n]), lens + n, optimize != 0);
             if (s != ES_OK) lens[n] = 0;
             status[n] = s;
         }
@@ -534,6 +671,11 @@ int dbn_jpeg_encode_batch(const short* coef, long coef_elems, const long long* d
         for (auto& th : pool) th.join();
     }
     return DBN_OK;
+}
+
+int dbn_jpeg_encode_batch(const short* coef, long coef_elems, const long long* desc, const unsigned short* qtabs, int N, int restart_interval,
+                          unsigned char* out, long out_bytes, const long long* offs, long long* lens, int* status, int threads) {
+    return dbn_jpeg_encode_batch_opt(coef, coef_elems, desc, qtabs, N, restart_interval, out, out_bytes, offs, lens, status, threads, 0);
 }
 
 }  // extern "C"

@@ -14,13 +14,17 @@ baseline decode (pinned against Pillow / libjpeg-turbo, tests/test_jpeg_cpu.py).
 
 Encode behind it, in the place of the reference's imageio / Pillow writes (utils.py:225,272,280, test_ocr.py:176,210,
 ts_request.py:38-39): the decoder turned round (csrc/jpeg_enc.hip).  Colour conversion, chroma downsampling, libjpeg's
-slow-integer forward DCT and quantisation run as gfx950 kernels, Huffman coding (Annex K tables) on the host threads;
-JpegCoefficients is the hand-over in both directions.  Bit for bit libjpeg's baseline output for the same settings
-(pinned against Pillow / libjpeg-turbo, tests/test_jpeg_encode_cpu.py).
+slow-integer forward DCT and quantisation run as gfx950 kernels, Huffman coding on the host threads or, with
+entropy='device', as gfx950 kernels too (csrc/jpeg_huff.hip: only the compressed scans cross to the host); the Annex K
+tables, or with optimize=True each image's own (libjpeg's optimize_coding).  JpegCoefficients is the hand-over in both
+directions.  Bit for bit libjpeg's baseline output for the same settings (pinned against Pillow / libjpeg-turbo,
+tests/test_jpeg_encode_cpu.py, tests/test_jpeg_optimize_cpu.py).
 
   quant_tables(quality)                    -> uint16 [2, 64] (jpeg_set_quality's scaling of the Annex K tables)
   forward_coefficients(images, ...)        -> JpegCoefficients (device half; decode_coefficients(...) of it is the lossy round trip)
   entropy_encode(obj, restart_interval)    -> [bytes] (host half; runs anywhere; entropy_encode(entropy_decode(x)) transcodes losslessly)
+  entropy_encode_device(obj, ...)          -> [bytes] (the same streams, coded on the device; coefficients on either side)
+  optimal_huffman_table(freq)              -> (counts [16], symbols): libjpeg's optimised table for 256 symbol counts
   encode_jpeg_batch(images, ...)           -> [bytes]; encode_jpeg(image, ...) -> bytes; save_jpegs(paths, images, ...) writes files
 
 Supported: baseline and 8-bit extended sequential Huffman streams, grey or YCbCr, 4:4:4 / 4:2:2 / 4:2:0, restart markers.
@@ -293,6 +297,7 @@ ENCODE_REASONS = {
     1: 'the image was not decoded, there are no coefficients to code', 2: 'descriptor and coefficient buffer disagree',
     3: 'a quantisation value lies outside 1 .. 255', 4: 'a DC difference needs more than 11 bits: not baseline-codable',
     5: 'an AC coefficient needs more than 10 bits: not baseline-codable', 6: 'the output slot is too small',
+    7: 'the optimised Huffman code would need more than 32 bits before limiting: libjpeg refuses it too',
 }
 # Annex K.1 / K.2, natural order
 _BASE_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
@@ -429,7 +434,7 @@ def forward_plan(items, subsampling, tables):
     return desc, qtabs, int(per.sum()), tp, tf
 
 
-def forward_coefficients(images, shapes=None, quality=75, subsampling='420', qtables=None, device=None):
+def forward_coefficients(images, shapes=None, quality=75, subsampling='420', qtables=None, device=None, host_copy=True):
     """Device half of the encode: uint8 images -> JpegCoefficients, libjpeg's quantised coefficients over the MCU-padded grid
     (dummy blocks as libjpeg codes them), copied into pinned host memory on the current stream; no host synchronisation
     (the result's wait() blocks until they have arrived; entropy_encode and decode_coefficients order themselves after it).
@@ -438,7 +443,9 @@ def forward_coefficients(images, shapes=None, quality=75, subsampling='420', qta
     uint8 [H, W, 3] / [N, H, W, 3] RGB; or uint8 [H, W] / [N, H, W] grey (a one-component stream); or a list of [H, W, 3]
     and [H, W] images of any sizes.  Tensors or arrays, on the host or the device.  A 3-D input whose last extent is 3 is
     one RGB image.  quality 1 .. 100 (quant_tables) or qtables: 1 to 3 tables [64] in natural order, values 1 .. 255, for
-    luma, Cb and Cr (the last one given serves the remaining components).  subsampling '444' | '422' | '420' for RGB."""
+    luma, Cb and Cr (the last one given serves the remaining components).  subsampling '444' | '422' | '420' for RGB.
+    host_copy=False: the coefficients stay on the device (`coef.is_cuda`; no pinned buffer, no copy), for
+    entropy_encode_device and decode_coefficients."""
     tables = _tables(quality, qtables)
     if device is not None:
         dev = torch.device(device)
@@ -459,8 +466,11 @@ def forward_coefficients(images, shapes=None, quality=75, subsampling='420', qta
         stream = torch.cuda.current_stream(dev)
         check(lib().dbn_jpeg_forward(flat.data_ptr(), flat.numel(), desc.data_ptr(), qt.data_ptr(), len(items), a.data_ptr(), len(tp),
                                      b.data_ptr(), len(tf), planes.data_ptr(), coef.data_ptr(), total, stream.cuda_stream), 'jpeg_forward')
-        host = torch.empty(total, dtype=torch.int16, pin_memory=True)
-        host.copy_(coef, non_blocking=True)
+        if host_copy:
+            host = torch.empty(total, dtype=torch.int16, pin_memory=True)
+            host.copy_(coef, non_blocking=True)
+        else:
+            host = coef
         ready = torch.cuda.Event()
         ready.record(stream)
     hdesc[:, _D_OUT] = np.cumsum(hdesc[:, _D_W] * hdesc[:, _D_H] * 3) - hdesc[:, _D_W] * hdesc[:, _D_H] * 3  # as entropy_decode leaves it
@@ -469,20 +479,123 @@ def forward_coefficients(images, shapes=None, quality=75, subsampling='420', qta
     return obj
 
 
-def entropy_encode(obj, restart_interval=0, threads=MAX_THREADS, errors='raise'):
+def optimal_huffman_table(freq):
+    """256 symbol counts -> (counts uint8 [16]: symbols per code length 1 .. 16, symbols uint8 [n] by length, then value): the
+    table libjpeg's jpeg_gen_optimal_table builds (a pseudo-symbol of count 1 keeps the all-ones code free, ties go to the
+    larger symbol, lengths are limited to 16), which is the payload of a DHT segment Pillow writes with optimize=True."""
+    f = np.asarray(freq)
+    if f.shape != (256, ) or f.dtype.kind not in 'iu' or f.min() < 0 or not f.any():
+        raise ValueError('freq is 256 non-negative integer counts, not all of them 0')
+    f = np.ascontiguousarray(f, np.int64)
+    bits, vals, n = np.zeros(16, np.uint8), np.zeros(256, np.uint8), np.zeros(1, np.int32)
+    check(lib().dbn_jpeg_optimal_table(f.ctypes.data, bits.ctypes.data, vals.ctypes.data, n.ctypes.data), 'jpeg_optimal_table')
+    return bits, vals[:int(n[0])].copy()
+
+
+def _check_encode_args(restart_interval, errors):
+    if errors not in ('raise', 'report'):
+        raise ValueError("errors is 'raise' or 'report'")
+    if isinstance(restart_interval, bool) or int(restart_interval) != restart_interval or not 0 <= int(restart_interval) <= 65535:
+        raise ValueError('restart_interval must be an integer in 0 .. 65535, got %r' % (restart_interval, ))
+    return int(restart_interval)
+
+
+def _encode_result(streams, status, errors):
+    errs = [None if s == 0 else JpegEncodeError(i, ENCODE_REASONS.get(int(s), 'status %d' % s), int(s)) for i, s in enumerate(status)]
+    if errors == 'raise':
+        for e in errs:
+            if e is not None:
+                raise e
+    streams = [None if e is not None else d for d, e in zip(streams, errs)]
+    return streams if errors == 'raise' else (streams, errs)
+
+
+def entropy_encode_device(obj, restart_interval=0, optimize=False, errors='raise', device=None):
+    """entropy_encode on the device (csrc/jpeg_huff.hip): the same byte strings, the same errors.  obj: a JpegCoefficients
+    whose coefficients are on the device (forward_coefficients(..., host_copy=False)) or on the host (they are uploaded:
+    entropy_encode_device(entropy_decode(datas)) transcodes without the DCT kernels).  The kernels run on the current
+    stream; the host waits once, for the lengths, and then copies the streams' own bytes.  optimize=True adds one round
+    trip before that: the per-image symbol histograms come to the host, which builds the tables."""
+    ri, N = _check_encode_args(restart_interval, errors), len(obj)
+    if N == 0:
+        raise ValueError('entropy_encode_device needs at least one image')
+    desc = np.ascontiguousarray(obj.desc, np.int64).copy()
+    desc[:, _D_STATUS] = np.asarray(obj.status)
+    qtabs = np.ascontiguousarray(obj.qtabs, np.uint16)
+    if obj.coef.dtype != torch.int16 or desc.shape != (N, _DESC) or qtabs.shape != (N, 3, 64):
+        raise ValueError('not the layout of JpegCoefficients')
+    if device is not None:
+        dev = torch.device(device)
+    elif obj.coef.is_cuda:
+        dev = obj.coef.device
+    else:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    if dev.type != 'cuda':
+        raise ValueError('entropy_encode_device runs on a GPU device, not %s' % dev)
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    L = lib()
+    blk, ivl = np.zeros(N + 1, np.int64), np.zeros(N + 1, np.int64)
+    status, sizes = np.zeros(N, np.int32), np.zeros(2, np.int64)
+    check(L.dbn_jpeg_huff_plan(desc.ctypes.data, qtabs.ctypes.data, N, obj.coef.numel(), ri, blk.ctypes.data, ivl.ctypes.data,
+                               status.ctypes.data, sizes.ctypes.data), 'jpeg_huff_plan')
+    total, intervals = int(blk[N]), int(ivl[N])
+    specs, codes = np.zeros((N if optimize else 1, 4, 273), np.uint16), np.zeros((N if optimize else 1, 4, 256), np.uint32)
+    scans = [b''] * N
+    if total:
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            if obj.ready is not None:
+                stream.wait_event(obj.ready)
+            coef = obj.coef.contiguous().to(dev, non_blocking=True)
+            ddesc, dblk, divl = _up(desc, dev), _up(blk, dev), _up(ivl, dev)
+            res = torch.full((2 * N + 1, ), -1, dtype=torch.int64, device=dev)
+            if optimize:
+                hist = torch.empty((N, 4, 256), dtype=torch.int32, device=dev)
+                check(L.dbn_jpeg_huff_hist(coef.data_ptr(), coef.numel(), ddesc.data_ptr(), N, dblk.data_ptr(), total, ri, hist.data_ptr(),
+                                           res.data_ptr(), stream.cuda_stream), 'jpeg_huff_hist')
+                hhist = hist.cpu().numpy().view(np.uint32)  # the one host step between launches
+                check(L.dbn_jpeg_huff_tables(hhist.ctypes.data, desc.ctypes.data, N, status.ctypes.data, specs.ctypes.data, codes.ctypes.data,
+                                             MAX_THREADS), 'jpeg_huff_tables')
+            else:
+                check(L.dbn_jpeg_huff_annex_k(specs.ctypes.data, codes.ctypes.data), 'jpeg_huff_annex_k')
+            dcodes = _up(codes.view(np.int32), dev)
+            ws = torch.empty(int(sizes[0]), dtype=torch.uint8, device=dev)
+            out = torch.empty(int(sizes[1]), dtype=torch.uint8, device=dev)
+            check(L.dbn_jpeg_huff_code(coef.data_ptr(), coef.numel(), ddesc.data_ptr(), N, dblk.data_ptr(), divl.data_ptr(), total, intervals, ri,
+                                       dcodes.data_ptr(), int(bool(optimize)), ws.data_ptr(), ws.numel(), out.data_ptr(), out.numel(),
+                                       res.data_ptr(), stream.cuda_stream), 'jpeg_huff_code')
+            hres = res.cpu().numpy().view(np.uint64)  # the one wait: error keys and offsets
+            offs = hres[N:].astype(np.int64)
+            if not (np.all(np.diff(offs) >= 0) and 0 <= offs[0] and offs[N] <= out.numel()):
+                raise RuntimeError('libdbnet_hip: jpeg_huff_code returned offsets outside its buffer')
+            blob = out[int(offs[0]):int(offs[N])].cpu().numpy()
+            blob = blob.tobytes()
+        bad = hres[:N] != np.uint64(0xFFFFFFFFFFFFFFFF)
+        status = np.where((status == 0) & bad, (hres[:N] & np.uint64(7)).astype(np.int32), status).astype(np.int32)
+        o0 = int(offs[0])
+        scans = [blob[int(a) - o0:int(b) - o0] for a, b in zip(offs[:-1], offs[1:])]
+    heads, hlens = np.zeros((N, 704), np.uint8), np.zeros(N, np.int64)
+    check(L.dbn_jpeg_huff_headers(desc.ctypes.data, qtabs.ctypes.data, N, ri, specs.ctypes.data, int(bool(optimize)), status.ctypes.data,
+                                  heads.ctypes.data, hlens.ctypes.data), 'jpeg_huff_headers')
+    streams = [heads[n, :int(hlens[n])].tobytes() + scans[n] + b'\xff\xd9' if status[n] == 0 else None for n in range(N)]
+    return _encode_result(streams, status, errors)
+
+
+def entropy_encode(obj, restart_interval=0, threads=MAX_THREADS, errors='raise', optimize=False):
     """Host half of the encode: JpegCoefficients -> list of JPEG byte strings (SOI, JFIF APP0, DQT, SOF0, DHT, DRI, SOS, one
     interleaved scan with the Annex K Huffman tables, EOI), on min(len(obj), 16, threads) threads.  Coefficients are
     taken as given, dummy blocks included: entropy_encode(entropy_decode(data), restart_interval=that stream's) reproduces
     the scan bytes of a stream that uses the Annex K tables.  restart_interval: MCUs between RSTn markers, 0 .. 65535.
     An image that cannot be coded raises JpegEncodeError(index, reason); errors='report': nothing raises; ->
-    (streams, errs) with streams[i] None and errs[i] the exception for such an image, which fails alone."""
-    if errors not in ('raise', 'report'):
-        raise ValueError("errors is 'raise' or 'report'")
-    if isinstance(restart_interval, bool) or int(restart_interval) != restart_interval or not 0 <= int(restart_interval) <= 65535:
-        raise ValueError('restart_interval must be an integer in 0 .. 65535, got %r' % (restart_interval, ))
-    ri, N = int(restart_interval), len(obj)
+    (streams, errs) with streams[i] None and errs[i] the exception for such an image, which fails alone.
+    optimize=True: every image is walked twice and carries its own Huffman tables, the ones libjpeg's optimize_coding
+    (Pillow's optimize=True) builds, in its four DHT segments (two for grey); everything else in the stream is unchanged."""
+    ri, N = _check_encode_args(restart_interval, errors), len(obj)
     if N == 0:
         raise ValueError('entropy_encode needs at least one image')
+    if obj.coef.is_cuda:
+        raise ValueError('the coefficients are on the device (host_copy=False): entropy_encode_device codes them there')
     obj.wait()
     coef = obj.coef.contiguous()
     desc = np.ascontiguousarray(obj.desc, np.int64).copy()
@@ -499,29 +612,30 @@ def entropy_encode(obj, restart_interval=0, threads=MAX_THREADS, errors='raise')
     offs[1:] = np.cumsum(per)
     out = np.empty(max(total, 1), np.uint8)  # the worst case; only the pages a stream reaches are ever touched
     lens, status = np.zeros(N, np.int64), np.zeros(N, np.int32)
-    check(L.dbn_jpeg_encode_batch(coef.data_ptr(), coef.numel(), desc.ctypes.data, qtabs.ctypes.data, N, ri, out.ctypes.data, total,
-                                  offs.ctypes.data, lens.ctypes.data, status.ctypes.data, int(threads)), 'jpeg_encode_batch')
-    errs = [None if s == 0 else JpegEncodeError(i, ENCODE_REASONS.get(int(s), 'status %d' % s), int(s)) for i, s in enumerate(status)]
-    if errors == 'raise':
-        for e in errs:
-            if e is not None:
-                raise e
-    streams = [None if e is not None else out[o:o + n].tobytes() for o, n, e in zip(offs[:-1], lens, errs)]
-    return streams if errors == 'raise' else (streams, errs)
+    check(L.dbn_jpeg_encode_batch_opt(coef.data_ptr(), coef.numel(), desc.ctypes.data, qtabs.ctypes.data, N, ri, out.ctypes.data, total,
+                                      offs.ctypes.data, lens.ctypes.data, status.ctypes.data, int(threads), int(bool(optimize))), 'jpeg_encode_batch')
+    return _encode_result([out[o:o + n].tobytes() for o, n in zip(offs[:-1], lens)], status, errors)
 
 
-def encode_jpeg_batch(images, shapes=None, quality=75, subsampling='420', qtables=None, restart_interval=0, threads=MAX_THREADS, device=None):
+def encode_jpeg_batch(images, shapes=None, quality=75, subsampling='420', qtables=None, restart_interval=0, threads=MAX_THREADS, device=None,
+                      optimize=False, entropy='host'):
     """uint8 images (the layouts of forward_coefficients) -> list of baseline JPEG byte strings.  The defaults are Pillow's /
     imageio's (quality 75, 4:2:0, the Annex K Huffman tables): the file decodes to the pixels of the file the reference's
-    imageio.imwrite(path, img) writes."""
-    return entropy_encode(forward_coefficients(images, shapes, quality, subsampling, qtables, device), restart_interval, threads)
+    imageio.imwrite(path, img) writes.  optimize=True: each image's own Huffman tables (Pillow's optimize=True).
+    entropy='host' codes on the host threads, 'device' on the GPU (no coefficient crosses to the host); the bytes are the same."""
+    if entropy not in ('host', 'device'):
+        raise ValueError("entropy is 'host' or 'device', got %r" % (entropy, ))
+    if entropy == 'device':
+        obj = forward_coefficients(images, shapes, quality, subsampling, qtables, device, host_copy=False)
+        return entropy_encode_device(obj, restart_interval, optimize)
+    return entropy_encode(forward_coefficients(images, shapes, quality, subsampling, qtables, device), restart_interval, threads, optimize=optimize)
 
 
-def encode_jpeg(image, quality=75, subsampling='420', qtables=None, restart_interval=0, device=None):
+def encode_jpeg(image, quality=75, subsampling='420', qtables=None, restart_interval=0, device=None, optimize=False, entropy='host'):
     """one uint8 [H, W, 3] (or grey [H, W]) image -> bytes"""
     if getattr(image, 'ndim', 0) not in (2, 3) or (image.ndim == 3 and image.shape[2] != 3):
         raise ValueError('encode_jpeg takes one uint8 [H, W, 3] or [H, W] image')
-    return encode_jpeg_batch([image], None, quality, subsampling, qtables, restart_interval, 1, device)[0]
+    return encode_jpeg_batch([image], None, quality, subsampling, qtables, restart_interval, 1, device, optimize, entropy)[0]
 
 
 def save_jpegs(paths, images, shapes=None, **kw):

@@ -876,6 +876,36 @@ int dbn_jpeg_forward(const unsigned char* pixels, long in_bytes, const long long
 long dbn_jpeg_encode_bound(const long long* desc, int N, int restart_interval, long long* per_image);
 int dbn_jpeg_encode_batch(const short* coef, long coef_elems, const long long* desc, const unsigned short* qtabs, int N, int restart_interval,
                           unsigned char* out, long out_bytes, const long long* offs, long long* lens, int* status, int threads);
+/* dbn_jpeg_optimal_table: freq int64 [256] -> bits uint8 [16], vals uint8 [256], *nvals: libjpeg's jpeg_gen_optimal_table (pseudo-symbol 256
+ * of count 1, ties to the larger symbol, lengths limited to 16, symbols by length then value): the DHT of Pillow's optimize=True.
+ * dbn_jpeg_encode_batch_opt: dbn_jpeg_encode_batch with `optimize`: not 0, each image is walked twice and carries its own tables in its DHT
+ * segments; status 7: libjpeg's builder would give up (a code of more than 32 bits).  optimize 0 gives dbn_jpeg_encode_batch's bytes. */
+int dbn_jpeg_optimal_table(const long long* freq, unsigned char* bits, unsigned char* vals, int* nvals);
+int dbn_jpeg_encode_batch_opt(const short* coef, long coef_elems, const long long* desc, const unsigned short* qtabs, int N, int restart_interval,
+                              unsigned char* out, long out_bytes, const long long* offs, long long* lens, int* status, int threads, int optimize);
+
+/* ---- Huffman coding on the device (csrc/jpeg_huff.hip): the scans of dbn_jpeg_encode_batch(_opt) from coefficients in device memory, parallel
+ * over the blocks of the batch in scan order; headers and EOI are the host's.  Tables travel as specs uint16 [4][273] (DC 0, AC 0, DC 1, AC 1:
+ * symbols per length [16], symbol count, symbols [256]) and codes uint32 [4][256] (code | length << 16).
+ * dbn_jpeg_huff_plan (host): status [N] (0, or the host coder's 1 / 2 / 3; such an image gets no blocks), blk_base / int_base int64 [N + 1] (first
+ * scan block / restart interval of each image over the batch), sizes int64 [2] = bytes of workspace and of output dbn_jpeg_huff_code wants.
+ * dbn_jpeg_huff_hist (device, one launch): hist uint32 [N][4][256], the symbol counts of each image's scan; errkey uint64 [N], all ones before
+ * the first call, lowered to (first failing scan block << 3 | status 4 / 5, or 2 for a descriptor the kernel did not follow).
+ * dbn_jpeg_huff_annex_k / dbn_jpeg_huff_tables (host): the Annex K set, or every image's own set from its histogram (status 7 as above).
+ * dbn_jpeg_huff_code (device, nine launches, no synchronisation): res uint64 [2 N + 1] = errkey [N], offs [N + 1]; image n's entropy-coded
+ * segment (stuffed, RSTn between intervals, ones-padded) is out[offs[n] .. offs[n + 1]).  coef, ws 16-byte aligned.
+ * dbn_jpeg_huff_headers (host): SOI .. SOS of image n into out[704 n ..], lens[n] its length (0 where status[n] is not 0). */
+int dbn_jpeg_huff_plan(const long long* desc, const unsigned short* qtabs, int N, long coef_elems, int restart_interval, long long* blk_base,
+                       long long* int_base, int* status, long long* sizes);
+int dbn_jpeg_huff_hist(const short* coef, long coef_elems, const long long* desc, int N, const long long* blk_base, long total_blocks,
+                       int restart_interval, unsigned* hist, unsigned long long* errkey, void* stream);
+int dbn_jpeg_huff_annex_k(unsigned short* specs, unsigned* codes);
+int dbn_jpeg_huff_tables(const unsigned* hist, const long long* desc, int N, int* status, unsigned short* specs, unsigned* codes, int threads);
+int dbn_jpeg_huff_code(const short* coef, long coef_elems, const long long* desc, int N, const long long* blk_base, const long long* int_base,
+                       long total_blocks, long total_intervals, int restart_interval, const unsigned* codes, int per_image, void* ws, long ws_bytes,
+                       unsigned char* out, long out_bytes, unsigned long long* res, void* stream);
+int dbn_jpeg_huff_headers(const long long* desc, const unsigned short* qtabs, int N, int restart_interval, const unsigned short* specs, int per_image,
+                          const int* status, unsigned char* out, long long* lens);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,10 @@ workloads the pipeline ends in, both 4:2:0 at quality 75:
   crops    9 600 word crops of 32 x 100 (crop_words' output)
 and prints, per workload: the device stage (both kernels, device events) against its algorithmic bytes (3 B per pixel in,
 2 B per coefficient out), the coefficient copy to pinned memory, the host stage at 1 and 16 threads, images/s end to end,
-and Pillow encoding the same arrays in 16 worker processes (when Pillow is installed).  Needs a GPU; there is no fallback.
+and Pillow encoding the same arrays in 16 worker processes (when Pillow is installed); then the device Huffman coder
+(csrc/jpeg_huff.hip): entropy_encode_device on coefficients that stayed on the device and the whole entropy='device' call,
+each against the host path at 16 threads in the same run, and the total file bytes with and without optimize.  Needs a
+GPU; there is no fallback.
 
   python tools/jpeg_encode_probe.py [--workload render|crops|both] [--reps 5] [--no-pillow]
 Run each workload as a step of its own under a time limit, e.g.
@@ -113,12 +116,34 @@ def probe(kind, reps, pillow):
         t0 = time.perf_counter()
         streams = J.encode_jpeg_batch(x)
         e2e.append(time.perf_counter() - t0)
+    # the device coder against the host path (the coefficient copy is part of the host path, not of the device one)
+    def timed(f):
+        ts = []
+        for _ in range(max(3, reps // 2 + 1)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = f()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return median(ts[1:]), r
+    dobj = J.forward_coefficients(x, host_copy=False)
+    dev_ms, dstreams = timed(lambda: J.entropy_encode_device(dobj))
+    dev_opt_ms, dopt = timed(lambda: J.entropy_encode_device(dobj, optimize=True))
+    host_opt_ms, hopt = timed(lambda: J.entropy_encode(obj, threads=16, optimize=True))
+    e2e_dev_ms, s2 = timed(lambda: J.encode_jpeg_batch(x, entropy='device'))
+    e2e_host_ms, s1 = timed(lambda: J.encode_jpeg_batch(x))
+    e2e_dev_opt_ms, _ = timed(lambda: J.encode_jpeg_batch(x, entropy='device', optimize=True))
+    e2e_host_opt_ms, _ = timed(lambda: J.encode_jpeg_batch(x, optimize=True))
+    assert dstreams == streams and s2 == s1 and dopt == hopt
+    device = dict(device_entropy_ms=dev_ms, device_entropy_optimize_ms=dev_opt_ms, host_entropy_optimize_ms_16_threads=host_opt_ms,
+                  end_to_end_device_ms=e2e_dev_ms, end_to_end_host_ms=e2e_host_ms, end_to_end_device_optimize_ms=e2e_dev_opt_ms,
+                  end_to_end_host_optimize_ms=e2e_host_opt_ms, jpeg_bytes_optimize=sum(len(d) for d in dopt),
+                  device_to_host_bytes_device_path=sum(len(d) for d in dstreams), device_to_host_bytes_host_path=total * 2)
     bytes_alg = n * h * w * 3 + total * 2
     res = dict(workload=kind, images=n, height=h, width=w, coefficients=total, algorithmic_bytes=bytes_alg,
                device_stage_ms=median(kern), device_stage_GBps=bytes_alg / median(kern) / 1e6, coefficient_copy_ms=median(copy),
                coefficient_copy_GBps=total * 2 / median(copy) / 1e6, host_stage_ms_1_thread=hostt[1], host_stage_ms_16_threads=hostt[16],
                end_to_end_images_per_s=n / median(e2e), end_to_end_ms=median(e2e) * 1e3, jpeg_bytes=sum(len(s) for s in streams),
-               planes_workgroups=len(tp), fdct_workgroups=len(tf))
+               planes_workgroups=len(tp), fdct_workgroups=len(tf), **device)
     if pillow:
         try:
             rate, dt = pillow_rate(arr)
