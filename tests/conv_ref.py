@@ -1,0 +1,310 @@
+"""float64 references of the convolution kernels that tests/test_conv_fp64_gpu.py pins (csrc/conv*.hip, wgrad*.hip, winograd*.hip), the
+two exact data sets of that module and the fp32 emulations that show WHY those data sets are exact.
+
+Plain torch on the CPU: explicit loops over the taps, one matmul over the channels per tap, strided slices of a zero-padded copy.  No
+F.conv2d, no autograd: tests/test_conv_ref_cpu.py checks every function here against those in float64, so that a wrong reference cannot
+make a GPU test pass.  Tensors are NCHW, weights OIHW (ConvTranspose2d: [Cin, Cout, k, k] as in PyTorch); every operand is expected in
+float64 already (the caller rounds to the kernel's operand type first, then .double())."""
+import torch
+
+
+def out_size(n, k, s, p):
+    return (n + 2 * p - k) // s + 1
+
+
+def _padded(x, p):
+    N, C, H, W = x.shape
+    xp = torch.zeros((N, C, H + 2 * p, W + 2 * p), dtype=x.dtype)
+    xp[:, :, p:p + H, p:p + W] = x
+    return xp
+
+
+def _tap(t, r, q, s, Ho, Wo):
+    """The pixels of a padded tensor that tap (r, q) pairs with the Ho x Wo output pixels (a view)."""
+    return t[:, :, r:r + s * (Ho - 1) + 1:s, q:q + s * (Wo - 1) + 1:s]
+
+
+def conv2d(x, w, b=None, stride=1, pad=0):
+    N, Ci, H, W = x.shape
+    Co, _, R, S = w.shape
+    Ho, Wo = out_size(H, R, stride, pad), out_size(W, S, stride, pad)
+    xp = _padded(x, pad)
+    y = torch.zeros((N, Co, Ho * Wo), dtype=x.dtype)
+    for r in range(R):
+        for q in range(S):
+            y += torch.matmul(w[:, :, r, q], _tap(xp, r, q, stride, Ho, Wo).reshape(N, Ci, Ho * Wo))
+    y = y.reshape(N, Co, Ho, Wo)
+    return y if b is None else y + b.view(1, Co, 1, 1)
+
+
+def conv2d_dgrad(dy, w, stride, pad, H, W):
+    """Gradient of conv2d(x [N, Ci, H, W], w) with respect to x."""
+    N, Co, Ho, Wo = dy.shape
+    _, Ci, R, S = w.shape
+    dxp = torch.zeros((N, Ci, H + 2 * pad, W + 2 * pad), dtype=dy.dtype)
+    d = dy.reshape(N, Co, Ho * Wo)
+    for r in range(R):
+        for q in range(S):
+            _tap(dxp, r, q, stride, Ho, Wo).add_(torch.matmul(w[:, :, r, q].t(), d).reshape(N, Ci, Ho, Wo))
+    return dxp[:, :, pad:pad + H, pad:pad + W].contiguous()
+
+
+def conv2d_wgrad(x, dy, R, S, stride, pad):
+    """Gradient of conv2d(x, w [Co, Ci, R, S]) with respect to w."""
+    N, Ci, H, W = x.shape
+    _, Co, Ho, Wo = dy.shape
+    xp = _padded(x, pad)
+    d = dy.reshape(N, Co, Ho * Wo)
+    dw = torch.zeros((Co, Ci, R, S), dtype=x.dtype)
+    for r in range(R):
+        for q in range(S):
+            dw[:, :, r, q] = torch.matmul(d, _tap(xp, r, q, stride, Ho, Wo).reshape(N, Ci, Ho * Wo).transpose(1, 2)).sum(0)
+    return dw
+
+
+def conv_transpose2d(x, w, b=None, stride=1, pad=0):
+    """nn.ConvTranspose2d (output_padding 0): x [N, Ci, H, W], w [Ci, Co, k, k] -> [N, Co, (H - 1) stride - 2 pad + k, ...]; every
+    input pixel adds x w[:, :, r, q] at output (h stride - pad + r, w stride - pad + q).  Pixels no tap reaches are 0 (+ bias)."""
+    N, Ci, H, W = x.shape
+    _, Co, R, S = w.shape
+    full = torch.zeros((N, Co, (H - 1) * stride + R, (W - 1) * stride + S), dtype=x.dtype)
+    xf = x.reshape(N, Ci, H * W)
+    for r in range(R):
+        for q in range(S):
+            _tap(full, r, q, stride, H, W).add_(torch.matmul(w[:, :, r, q].t(), xf).reshape(N, Co, H, W))
+    y = full[:, :, pad:full.shape[2] - pad, pad:full.shape[3] - pad].contiguous()
+    return y if b is None else y + b.view(1, Co, 1, 1)
+
+
+def accumulate(base, y):
+    """The accumulate form of every kernel: dst = dst + result."""
+    return base + y
+
+
+def rms(t):
+    return float(t.double().pow(2).mean().sqrt())
+
+
+def bf16_rne(t):
+    """fp32 -> nearest bf16 (ties to even) in integer arithmetic, as float32 (the rounding csrc/igemm_common.h bf16_bits_rne documents)."""
+    u = t.float().contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    u = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
+    return (u - ((u >> 31) << 32)).to(torch.int32).view(torch.float32)
+
+
+# ---- the exact data sets ------------------------------------------------------------------------------------------------------------
+def _ints(shape, lo, hi, seed):
+    return torch.randint(lo, hi + 1, shape, generator=torch.Generator().manual_seed(seed)).double()
+
+
+def dense_x(shape, seed):
+    """{-4 .. 4} / 4."""
+    return _ints(shape, -4, 4, seed) / 4
+
+
+def dense_w(shape, seed, winograd=False):
+    """{-8 .. 8} / 8; for Winograd multiples of 1 / 2 in [-1, 1], so that G g G^T (entries of G: 1, 1/2) stays on a 2^-3 grid."""
+    return _ints(shape, -2, 2, seed) / 2 if winograd else _ints(shape, -8, 8, seed) / 8
+
+
+def dense_bias(n, seed):
+    """Multiples of 1 / 32 in [-1, 1]."""
+    return _ints((n, ), -32, 32, seed) / 32
+
+
+def distinct_w(Co, Ci, R, S, seed=0):
+    """m / 128 with odd |m| <= 127 and, within any window of 128 consecutive (co, ci, tap) indices, 128 distinct values: a term that
+    lands at the wrong output channel, input channel or tap changes the result instead of cancelling.  8 significant bits at the most:
+    exact in bf16 and fp16."""
+    n = Co * Ci * R * S
+    i = (torch.arange(n) * 37 + seed) % 128  # 37 is odd: a bijection of every run of 128 indices
+    m = torch.where(i < 64, 2 * i + 1, -(2 * (i - 64) + 1))
+    return (m.double() / 128).reshape(Co, Ci, R, S)
+
+
+IMPULSE_VALUES = (1.0, -2.0, 0.5)
+M_TILES = (64, 128, 256)  # rows of the library's M tiles (csrc/igemm_kernel.h launch_igemm_ns: BM)
+
+
+def seam_pixels(N, H, W, Hd, Wd, stride, tile_rows=64, extra=()):
+    """Pixels (n, h, w) of an [N, H, W] map on the seams of a kernel that walks the [N, Hd, Wd] map on the other side of a stride-`stride`
+    convolution in tiles of `tile_rows` flattened pixels (a divisor of every M tile, so that every tile's boundaries are among them): the
+    first and last pixel of every image, the pixel on each side of every tile boundary and, for stride 2, one pixel of each parity class; `extra` adds (h, w)
+    pairs to every image."""
+    assert all(t % tile_rows == 0 for t in M_TILES), tile_rows
+    big = H >= Hd  # this map is the finer one: a pixel of the other map lies at (h stride, w stride) here
+    pts = []
+    for n in range(N):
+        pts += [(n, 0, 0), (n, H - 1, W - 1)]
+        pts += [(n, h, w) for (h, w) in extra if h < H and w < W]
+    if stride == 2 and H > 4 and W > 4:
+        pts += [(0, H // 2 | 1, W // 2 | 1), (0, H // 2 | 1, (W // 2 | 1) - 1), (N - 1, (H // 2 | 1) - 1, W // 2 | 1), (N - 1, (H // 2 | 1) - 1, (W // 2 | 1) - 1)]
+    for m in range(tile_rows, N * Hd * Wd, tile_rows):
+        for mm in (m - 1, m):
+            n, hd, wd = mm // (Hd * Wd), mm // Wd % Hd, mm % Wd
+            h, w = (hd * stride, wd * stride) if big else (hd // stride, wd // stride)
+            pts.append((n, min(h, H - 1), min(w, W - 1)))
+    return sorted(set(pts))
+
+
+def separate(pts, dist):
+    """Greedy split of the pixels into sets in which two pixels of one image differ by >= dist in h or in w: no output of a kernel
+    with a support below dist sees two of them."""
+    sets = []
+    for p in pts:
+        for s in sets:
+            if all(q[0] != p[0] or max(abs(q[1] - p[1]), abs(q[2] - p[2])) >= dist for q in s):
+                s.append(p)
+                break
+        else:
+            sets.append([p])
+    return sets
+
+
+def impulse_maps(N, C, H, W, pts, dist, two_channels=True):
+    """One [N, C, H, W] map per set of separate(pts, dist): zero except at the set's pixels, which carry a value of IMPULSE_VALUES in
+    channel C - 1 (the last real channel) or, in turn, in another channel — and, with two_channels, every third pixel in both."""
+    maps = []
+    j = 0
+    for s in separate(pts, dist):
+        x = torch.zeros((N, C, H, W), dtype=torch.float64)
+        for (n, h, w) in s:
+            v = IMPULSE_VALUES[j % 3]
+            other = (5 * j + 1) % C
+            both = two_channels and j % 3 == 0
+            if both or j % 2 == 0:
+                x[n, C - 1, h, w] = v
+            if both or j % 2 == 1:
+                x[n, other, h, w] = IMPULSE_VALUES[(j + 1) % 3] if both else v
+            j += 1
+        maps.append(x)
+    return maps
+
+
+def representable(t, dtype):
+    return bool((t.to(dtype).double() == t.double()).all())
+
+
+# ---- why the data sets are exact: fp32 evaluation in three summation orders ----------------------------------------------------------
+def conv_terms(x, w, stride, pad):
+    """The products of conv2d in float32: cols [M, K], wk [K, Co] with K = (tap, channel) — term k of output (m, co) is cols[m, k] wk[k, co]."""
+    N, Ci, H, W = x.shape
+    Co, _, R, S = w.shape
+    Ho, Wo = out_size(H, R, stride, pad), out_size(W, S, stride, pad)
+    xp = _padded(x, pad)
+    cols = torch.stack([_tap(xp, r, q, stride, Ho, Wo) for r in range(R) for q in range(S)], 0)  # [RS, N, Ci, Ho, Wo]
+    cols = cols.permute(1, 3, 4, 0, 2).reshape(N * Ho * Wo, R * S * Ci)
+    wk = w.permute(2, 3, 1, 0).reshape(R * S * Ci, Co)
+    return cols.float(), wk.float()
+
+
+def fp32_sums(cols, wk, block=64):
+    """sum_k cols[m, k] wk[k, co] evaluated in float32 three ways — forward, reversed and pairwise (a binary tree) — every product and every
+    addition rounded to float32 (elementwise float32 ops; no matmul, whose order is the library's own business).  [3, M, Co]."""
+    M, K = cols.shape
+    Co = wk.shape[1]
+    fwd = torch.zeros((M, Co), dtype=torch.float32)
+    rev = torch.zeros((M, Co), dtype=torch.float32)
+    for k in range(K):
+        fwd += cols[:, k, None] * wk[None, k]
+        rev += cols[:, K - 1 - k, None] * wk[None, K - 1 - k]
+    pair = torch.zeros((M, Co), dtype=torch.float32)
+    for m0 in range(0, M, block):
+        t = cols[m0:m0 + block, :, None] * wk[None]  # [block, K, Co]
+        while t.shape[1] > 1:
+            if t.shape[1] % 2:
+                t = torch.cat([t, torch.zeros_like(t[:, :1])], 1)
+            t = t[:, 0::2] + t[:, 1::2]
+        pair[m0:m0 + block] = t[:, 0]
+    return torch.stack([fwd, rev, pair])
+
+
+def abs_sum_bound(x, w, stride, pad):
+    """max over the outputs of sum |term|: bounds every partial sum of every summation order."""
+    return float(conv2d(x.abs(), w.abs(), None, stride, pad).max())
+
+
+# ---- Winograd F(2x2, 3x3) in float32 -------------------------------------------------------------------------------------------------
+BT = torch.tensor([[1., 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]])
+G = torch.tensor([[1., 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]])
+AT = torch.tensor([[1., 1, 1, 0], [0, 1, -1, -1]])
+
+
+def _mm32(a, b):
+    """a @ b with every product and every addition rounded to float32, summed in index order (broadcast elementwise ops)."""
+    out = torch.zeros(a.shape[:-1] + b.shape[-1:], dtype=torch.float32)
+    for k in range(a.shape[-1]):
+        out = out + a[..., :, k, None] * b[..., k, None, :]
+    return out
+
+
+def winograd_fp32(x, w, b=None):
+    """3x3 / stride 1 / pad 1 convolution through Winograd F(2x2, 3x3), every step in float32: V = B^T d B per 4 x 4 input tile,
+    U = G g G^T per filter, M = sum_ci U V (forward channel order), y = A^T M A.  Returns (y, V, U, M) as float32; the caller compares
+    each with the same quantity in float64 (winograd_fp64)."""
+    return _winograd(x.float(), w.float(), None if b is None else b.float(), torch.float32)
+
+
+def winograd_fp64(x, w, b=None):
+    return _winograd(x.double(), w.double(), None if b is None else b.double(), torch.float64)
+
+
+def _winograd(x, w, b, dt):
+    N, Ci, H, W = x.shape
+    Co = w.shape[0]
+    th, tw = (H + 1) // 2, (W + 1) // 2
+    xp = torch.zeros((N, Ci, 2 * th + 2, 2 * tw + 2), dtype=dt)
+    xp[:, :, 1:H + 1, 1:W + 1] = x
+    d = torch.stack([torch.stack([xp[:, :, i:i + 2 * th:2, j:j + 2 * tw:2] for j in range(4)], -1) for i in range(4)], -2)  # [N, Ci, th, tw, 4, 4]
+    bt, g, at = BT.to(dt), G.to(dt), AT.to(dt)
+    mm = _mm32 if dt == torch.float32 else torch.matmul
+    V = mm(mm(bt.expand(N, Ci, th, tw, 4, 4), d), bt.t().expand(N, Ci, th, tw, 4, 4))
+    U = mm(mm(g.expand(Co, Ci, 4, 3), w), g.t().expand(Co, Ci, 3, 4))  # [Co, Ci, 4, 4]
+    M = torch.zeros((N, Co, th, tw, 4, 4), dtype=dt)
+    for ci in range(Ci):
+        M = M + U[None, :, ci, None, None] * V[:, None, ci]
+    y4 = mm(mm(at.expand(N, Co, th, tw, 2, 4), M), at.t().expand(N, Co, th, tw, 4, 2))  # [N, Co, th, tw, 2, 2]
+    y = y4.permute(0, 1, 2, 4, 3, 5).reshape(N, Co, 2 * th, 2 * tw)[:, :, :H, :W]
+    if b is not None:
+        y = y + b.view(1, Co, 1, 1)
+    return y.contiguous(), V, U, M
+
+
+# ---- the cases of tests/test_conv_fp64_gpu.py (checked on the CPU in tests/test_conv_ref_cpu.py) ---------------------------------------
+# N, Ci, Co, k, stride, pad, H, W
+FWD_CASES = [
+    (2, 64, 64, 3, 1, 1, 16, 12),  # the baseline
+    (3, 128, 64, 1, 1, 0, 9, 7),  # M = 189 straddles every M tile
+    (1, 64, 128, 3, 2, 1, 18, 14),  # stride 2, even map
+    (1, 64, 64, 3, 2, 1, 17, 13),  # stride 2, odd map
+    (2, 3, 64, 7, 2, 3, 32, 40),  # the stem: Ci padded to 4
+    (1, 256, 256, 3, 1, 1, 12, 12),  # K = 2304
+    (1, 512, 512, 3, 1, 1, 2, 2),  # K = 4608 on a map smaller than the halo
+    (1, 64, 192, 3, 1, 1, 10, 9),  # Co = 192 crosses a 128 tile and is no multiple of 256
+    (1, 64, 64, 3, 1, 1, 16, 32),  # Hd % 8 == 0, Wd % 16 == 0, Cs % 32 == 0: the 8 x 16 pixel-patch kernels (csrc/conv.hip patch_eligible)
+]
+DGRAD_CASES = [c for c in FWD_CASES if c[1] % 64 == 0]  # the gradient's channel count Ci is the kernel's Cd: a multiple of 64
+WGRAD_CASES = [FWD_CASES[i] for i in (0, 2, 3, 4, 5, 6)]  # those of tests/test_ops_gpu.py WGRAD_CASES
+SPLITK_CASES = [(1, 512, 512, 3, 1, 1, 10, 12), (2, 256, 64, 10, 8, 1, 40, 40)]
+KSPLITS = (2, 5, 7)
+CONVT2 = (2, 64, 64, 8, 6)  # N, Ci, Co, H, W: ConvTranspose2d(k = 2, stride 2)
+CONVT_GENERAL = [(4, 6, 1), (8, 2, 0)]  # (stride, k, pad) on CONVT_GENERAL_SHAPE
+CONVT_GENERAL_SHAPE = (2, 64, 128, 5, 7)
+WINOGRAD_CASES = [(2, 64, 64, 13, 30), (2, 64, 64, 20, 20)]  # N, Ci, Co, H, W
+WINOGRAD_SEAM_CASES = [(3, 64, 64, 20, 20), (1, 64, 64, 10, 9), (2, 64, 64, 13, 30)]  # consecutive-tile form (two), ragged 8 x 16 patches
+
+
+def winograd_seams(N, H, W):
+    """Pixels on the seams of the Winograd kernels' walk: image corners, the four pixels around the first 8 x 16 patch corner, the last
+    row and column, and the first and last 2 x 2 tile of every group of 32 consecutive tiles (the small-map form numbers the tiles
+    through the whole batch)."""
+    th, tw = (H + 1) // 2, (W + 1) // 2
+    pts = []
+    for n in range(N):
+        pts += [(n, 0, 0), (n, H - 1, W - 1), (n, H - 1, 0), (n, 0, W - 1), (n, H - 1, W // 2), (n, H // 2, W - 1)]
+        pts += [(n, h, w) for h in (7, 8) for w in (15, 16) if h < H and w < W]
+    total = N * th * tw
+    for g in sorted(set(list(range(31, total, 32)) + list(range(32, total, 32)) + [total - 1])):
+        n, t = g // (th * tw), g % (th * tw)
+        pts.append((n, min(2 * (t // tw), H - 1), min(2 * (t % tw), W - 1)))
+    return sorted(set(pts))

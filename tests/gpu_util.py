@@ -63,6 +63,35 @@ def igemm(src, wpk, bias, dst, R, stride, pad, mode, accumulate=0, tile=0, ns=0)
         _lib.check(L().dbn_igemm_bf16s(*args, ns, stream()), 'igemm_bf16s')
 
 
+AT_OF = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+
+
+def igemm_t(src, wpk, bias, dst, R, stride, pad, mode, accumulate=0, tile=0, ns=1, ksplit=1, slab=None):
+    N, Hs, Ws, Cs = src.shape
+    _, Hd, Wd, Cd = dst.shape
+    _lib.check(L().dbn_igemm_t(AT_OF[src.dtype], ns, src.data_ptr(), wpk.data_ptr(), None if bias is None else bias.data_ptr(), dst.data_ptr(),
+                               N, Hs, Ws, Cs, Hd, Wd, Cd, R, R, stride, pad, mode, accumulate, tile, ksplit,
+                               None if slab is None else slab.data_ptr(), stream()), 'igemm_t')
+
+
+def pack_t(w, mode, stride, kind, cs=0):
+    O, I, R, S = w.shape
+    wd = w.contiguous().to(DEV)
+    out = torch.empty(L().dbn_igemm_panel_floats_t(kind, O, I, R, S, mode, stride, cs), device=DEV)
+    _lib.check(L().dbn_pack_weights_t(kind, wd.data_ptr(), O, I, R, S, mode, stride, cs, out.data_ptr(), stream()), 'pack_t')
+    return out
+
+
+def igemm_splitk(src, wpk, bias, dst, R, stride, pad, mode, ksplit, accumulate=0, tile=0, ns=0):
+    """dbn_igemm_splitk_f32 with a NaN-filled slab."""
+    N, Hs, Ws, Cs = src.shape
+    _, Hd, Wd, Cd = dst.shape
+    slab = torch.full((L().dbn_igemm_splitk_slab_floats(ksplit, N, Hd, Wd, Cd), ), float('nan'), device=DEV)
+    _lib.check(L().dbn_igemm_splitk_f32(src.data_ptr(), wpk.data_ptr(), None if bias is None else bias.data_ptr(), dst.data_ptr(), N, Hs, Ws,
+                                        Cs, Hd, Wd, Cd, R, R, stride, pad, mode, accumulate, tile, ns, ksplit, slab.data_ptr(), stream()),
+               'splitk')
+
+
 def wgrad(sm, big, O, I, k, stride, pad, scale=1.0, ns=0):
     N, Ho, Wo, _ = sm.shape
     _, H, W, Cb = big.shape
@@ -165,3 +194,23 @@ def exact(tag, got, ref):
                 first = (i + j, float(g[j]), float(r[j]))
     assert nne == 0, '%s: %d of %d elements differ; the first at %d: got %r ref %r' % ((tag, nne, got.numel()) + first)
     print('%s: %d elements bit-exact' % (tag, got.numel()))
+
+
+def distance_ratio(tag, got, ref64, ref32, margin, allow=None):
+    """The kernel's distance to float64 against plain fp32's own: rms(got - ref64) <= margin rms(ref32 - ref64) and
+    max |got - ref64| <= margin max |ref32 - ref64|; got finite everywhere.  allow (16-bit storage): an elementwise allowance for the one
+    output rounding, taken off |got - ref64| first.  Prints and returns the two ratios."""
+    got, ref64, ref32 = got.detach().cpu().double(), ref64.detach().cpu().double(), ref32.detach().cpu().double()
+    assert got.shape == ref64.shape == ref32.shape, (tag, got.shape, ref64.shape, ref32.shape)
+    nf = ~torch.isfinite(got)
+    assert not bool(nf.any()), '%s: %d non-finite elements, the first at %d' % (tag, int(nf.sum()), int(nf.reshape(-1).nonzero()[0]))
+    err = (got - ref64).abs()
+    if allow is not None:
+        err = (err - allow).clamp_min(0)
+    e32 = (ref32 - ref64).abs()
+    r_rms = float(err.pow(2).mean().sqrt() / e32.pow(2).mean().sqrt())
+    r_max = float(err.max() / e32.max())
+    msg = 'RATIO %s: rms %.3f max %.3f (fp32 itself: rms %.3e max %.3e)' % (tag, r_rms, r_max, float(e32.pow(2).mean().sqrt()), float(e32.max()))
+    print(msg)
+    assert r_rms <= margin and r_max <= margin, msg + ' over the margin %g' % margin
+    return r_rms, r_max

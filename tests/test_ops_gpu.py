@@ -6,7 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import DEV, L, col_sum_depth, igemm, nchw, nhwc, pack, reduce_ws, report, rnd, stream, wgrad
+from gpu_util import AT_OF, DEV, L, col_sum_depth, igemm, igemm_t, nchw, nhwc, pack, pack_t, reduce_ws, report, rnd, stream, wgrad
 from db_text_minimal_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -1124,25 +1124,6 @@ def test_image_chunking_beyond_the_index_ranges():
         else:
             assert torch.equal(got[k], v), k
             assert torch.equal(got1[k], v), k
-
-
-AT_OF = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
-
-
-def igemm_t(src, wpk, bias, dst, R, stride, pad, mode, accumulate=0, tile=0, ns=1, ksplit=1, slab=None):
-    N, Hs, Ws, Cs = src.shape
-    _, Hd, Wd, Cd = dst.shape
-    _lib.check(L().dbn_igemm_t(AT_OF[src.dtype], ns, src.data_ptr(), wpk.data_ptr(), None if bias is None else bias.data_ptr(), dst.data_ptr(),
-                               N, Hs, Ws, Cs, Hd, Wd, Cd, R, R, stride, pad, mode, accumulate, tile, ksplit,
-                               None if slab is None else slab.data_ptr(), stream()), 'igemm_t')
-
-
-def pack_t(w, mode, stride, kind, cs=0):
-    O, I, R, S = w.shape
-    wd = w.contiguous().to(DEV)
-    out = torch.empty(L().dbn_igemm_panel_floats_t(kind, O, I, R, S, mode, stride, cs), device=DEV)
-    _lib.check(L().dbn_pack_weights_t(kind, wd.data_ptr(), O, I, R, S, mode, stride, cs, out.data_ptr(), stream()), 'pack_t')
-    return out
 
 
 @pytest.mark.parametrize('case', [(8, 200, 64, 256, 1, 1, 0, 0), (8, 200, 64, 256, 1, 1, 0, 1), (8, 200, 128, 128, 3, 2, 1, 1), (8, 50, 2304, 256, 1, 1, 0, 1),
