@@ -32,7 +32,7 @@ import torch
 
 from ._lib import check, lib
 from .gt_maps import GT_KEYS, MEAN, make_gt_maps, plan_polygons
-from .jpeg import JpegCoefficients, decode_coefficients
+from .jpeg import JpegCoefficients, JpegStreams, decode_coefficients, entropy_decode_device
 
 ROTATE = (-10.0, 10.0)  # data_loaders.py:62-66
 SCALE = (0.5, 3.0)
@@ -407,6 +407,11 @@ class DeviceBatches:
 
     def convert(self, batch):
         packed, shapes, polys, tags = batch
+        if isinstance(packed, JpegStreams):  # jpeg_stream_collate: the Huffman stage on the device too
+            packed = entropy_decode_device(packed, self.device)
+            for e in packed.errors():
+                if e is not None:
+                    raise e
         if isinstance(packed, JpegCoefficients):  # jpeg_collate: the device half of the decode
             packed, shapes = decode_coefficients(packed, self.device)
         if self.training:

@@ -7,6 +7,8 @@
 //                                    per image and component the blocks of the MCU-padded grid in raster order, 64
 //                                    coefficients each in NATURAL (de-zigzagged) order — plus an int64 descriptor per image,
 //                                    one quantisation table per component and a status per image (a corrupt file fails alone)
+//           dbn_jpeg_stream_plan     the host half of the device entropy stage (jpeg_dhuff.hip): the same headers, and the scans
+//                                    cut at their markers into restart intervals, without reading a bit of the entropy data
 //   device  dbn_jpeg_pixels          two kernels on one stream: jpeg_idct_kernel (dequantise, libjpeg's slow-integer 8 x 8
 //                                    inverse DCT, + 128, clamp -> uint8 sample planes in a workspace) and jpeg_rgb_kernel
 //                                    ("fancy" triangle chroma upsampling over the true downsampled size, YCbCr -> RGB or
@@ -28,6 +30,7 @@
 #include <vector>
 
 #include "common.h"
+#include "jpeg_dhuff.h"
 
 namespace {
 
@@ -374,6 +377,62 @@ int decode_scan(const unsigned char* d, long n, const Header& hd, short* coef) {
     return JS_OK;
 }
 
+// ---- host: descriptors ----------------------------------------------------------------------------------------------------
+// image n's descriptor and quantisation tables; co / oo: where its coefficients and its pixels start, moved on behind
+// them.  false: the coefficients do not fit into coef_elems.
+bool describe(const Header& hd, int n, long coef_elems, long& co, long& oo, long long* d, unsigned short* q) {
+    for (int i = 0; i < JP_DESC; ++i) d[i] = 0;
+    memset(q, 0, 192 * sizeof(unsigned short));
+    d[D_STATUS] = hd.status;
+    d[D_COEF] = co, d[D_OUT] = oo, d[D_QT] = (long)n * 192;
+    if (hd.status != JS_OK) return true;
+    if (co + hd.coef_elems() > coef_elems) return false;
+    d[D_W] = hd.width, d[D_H] = hd.height, d[D_NC] = hd.ncomp;
+    for (int c = 0; c < hd.ncomp; ++c) {
+        d[D_COMP + 4 * c] = hd.bw[c], d[D_COMP + 4 * c + 1] = hd.bh[c], d[D_COMP + 4 * c + 2] = hd.sh[c], d[D_COMP + 4 * c + 3] = hd.sv[c];
+        memcpy(q + 64 * c, hd.qt[hd.tq[c]], 64 * sizeof(unsigned short));
+    }
+    d[D_HMAX] = hd.hmax, d[D_VMAX] = hd.vmax, d[D_MCUX] = hd.mcux, d[D_MCUY] = hd.mcuy, d[D_RI] = hd.ri;
+    co += hd.coef_elems();
+    oo += (long)hd.width * hd.height * 3;
+    return true;
+}
+
+// ---- host: the plan of the device entropy stage (jpeg_dhuff.hip) ---------------------------------------------------------------
+// The restart intervals of a parsed, supported stream, found from the FF xx pairs of its scan alone: no bit of the entropy
+// data is looked at.  rows: DH_SEG int64 per interval (offsets relative to `d`), or nullptr to count.  -> the number of
+// intervals, or -1 when the markers are not the ones the header calls for (a marker missing, one too many, a wrong RSTn,
+// fill bytes, the end of the data): such a scan is the host decoder's.
+long scan_segments(const unsigned char* d, long n, const Header& hd, std::vector<long long>* rows) {
+    using namespace dbn_dhuff;
+    const long mcus = (long)hd.mcux * hd.mcuy;
+    const long want = hd.ri ? (mcus + hd.ri - 1) / hd.ri : 1;
+    long p = hd.scan_start, first = p, k = 0;
+    for (;;) {
+        const unsigned char* f = p < n ? (const unsigned char*)memchr(d + p, 0xFF, (size_t)(n - p)) : nullptr;
+        if (!f) return -1;
+        const long q = f - d;
+        if (q + 1 >= n) return -1;
+        const int m = d[q + 1];
+        if (m == 0) {
+            p = q + 2;
+            continue;
+        }
+        if (m == 0xFF) return -1;
+        if ((q - first) * 8 > 0xFFFFFFF0L) return -1;
+        const bool rst = m >= 0xD0 && m <= 0xD7;
+        if (rst ? (k >= want - 1 || m != 0xD0 + (int)(k & 7)) : k != want - 1) return -1;
+        if (rows) {
+            const long long row[DH_SEG] = {0, first, q, hd.ri ? k * hd.ri : 0, hd.ri ? (mcus - k * hd.ri < hd.ri ? mcus - k * hd.ri : hd.ri) : mcus,
+                                           k ? (k - 1) & 7 : -1};
+            rows->insert(rows->end(), row, row + DH_SEG);
+        }
+        ++k;
+        if (!rst) return k;
+        first = p = q + 2;
+    }
+}
+
 // ---- device -------------------------------------------------------------------------------------------------------------
 struct Img {
     long long coef, out, qt;
@@ -644,22 +703,8 @@ int dbn_jpeg_entropy_batch(const unsigned char* blob, const long long* offs, int
     for (int n = 0; n < N; ++n) {
         Header& hd = hds[n];
         parse_header(blob + offs[n], (long)(offs[n + 1] - offs[n]), hd);
-        long long* d = desc + (long)n * JP_DESC;
-        for (int i = 0; i < JP_DESC; ++i) d[i] = 0;
-        unsigned short* q = qtabs + (long)n * 192;
-        memset(q, 0, 192 * sizeof(unsigned short));
-        d[D_STATUS] = status[n] = hd.status;
-        d[D_COEF] = co, d[D_OUT] = oo, d[D_QT] = (long)n * 192;
-        if (hd.status != JS_OK) continue;
-        if (co + hd.coef_elems() > coef_elems) return DBN_ERR_ARG;
-        d[D_W] = hd.width, d[D_H] = hd.height, d[D_NC] = hd.ncomp;
-        for (int c = 0; c < hd.ncomp; ++c) {
-            d[D_COMP + 4 * c] = hd.bw[c], d[D_COMP + 4 * c + 1] = hd.bh[c], d[D_COMP + 4 * c + 2] = hd.sh[c], d[D_COMP + 4 * c + 3] = hd.sv[c];
-            memcpy(q + 64 * c, hd.qt[hd.tq[c]], 64 * sizeof(unsigned short));
-        }
-        d[D_HMAX] = hd.hmax, d[D_VMAX] = hd.vmax, d[D_MCUX] = hd.mcux, d[D_MCUY] = hd.mcuy, d[D_RI] = hd.ri;
-        co += hd.coef_elems();
-        oo += (long)hd.width * hd.height * 3;
+        status[n] = hd.status;
+        if (!describe(hd, n, coef_elems, co, oo, desc + (long)n * JP_DESC, qtabs + (long)n * 192)) return DBN_ERR_ARG;
     }
     int T = threads < 1 ? 1 : threads;
     T = T > 16 ? 16 : T;
@@ -704,6 +749,86 @@ int dbn_jpeg_pixels(const short* coef, long coef_elems, const long long* desc, c
     hipLaunchKernelGGL(jpeg_rgb_kernel, dim3((unsigned)n_rgb), dim3(RGB_THREADS), 0, (hipStream_t)stream, planes, coef_elems, desc, N, qt_elems,
                        tab_rgb, out, out_bytes);
     return dbn_status();
+}
+
+// The host half of the device entropy stage: headers as dbn_jpeg_entropy_batch parses them (same kinds, same status
+// codes), and the scans cut at their markers.  desc / qtabs / status: as dbn_jpeg_entropy_batch writes them, for headers
+// alone (what is wrong inside a scan is found later, by the device or by the host decoder it falls back to).  hspec uint8
+// [N][8][273], info int64 [N][8], seg int64 [seg_cap][6], sub_base int64 [seg_cap + 1] (first subsequence of each segment,
+// numbered over the batch), wgtab int32 [wg_cap][4] = {image, first subsequence, count, 0}: csrc/jpeg_dhuff.h.  seg ==
+// nullptr counts only.  counts int64 [4] = {segments, subsequences, workgroups, int16 coefficients}.
+int dbn_jpeg_stream_plan(const unsigned char* blob, const long long* offs, int N, long long* desc, unsigned short* qtabs, int* status,
+                         unsigned char* hspec, long long* info, long long* seg, long seg_cap, long long* sub_base, int* wgtab, long wg_cap,
+                         long long* counts) {
+    using namespace dbn_dhuff;
+    DBN_REQUIRE(blob && offs && desc && qtabs && status && hspec && info && counts && N > 0);
+    DBN_REQUIRE(!seg || (sub_base && wgtab && seg_cap >= 0 && wg_cap >= 0));
+    for (int n = 0; n < N; ++n) DBN_REQUIRE(offs[n] >= 0 && offs[n + 1] >= offs[n]);
+    Header* hd = new Header;
+    std::vector<long long> rows;
+    long co = 0, oo = 0, nseg = 0, nsub = 0, nwg = 0;
+    int rc = DBN_OK;
+    for (int n = 0; n < N && rc == DBN_OK; ++n) {
+        *hd = Header();
+        const unsigned char* d = blob + offs[n];
+        const long len = (long)(offs[n + 1] - offs[n]);
+        parse_header(d, len, *hd);
+        status[n] = hd->status;
+        describe(*hd, n, co + hd->coef_elems(), co, oo, desc + (long)n * JP_DESC, qtabs + (long)n * 192);
+        unsigned char* hs = hspec + (long)n * 8 * DH_SPEC;
+        memset(hs, 0, 8 * DH_SPEC);
+        long long* in = info + (long)n * DH_INFO;
+        for (int i = 0; i < DH_INFO; ++i) in[i] = 0;
+        in[DI_BEGIN] = offs[n], in[DI_END] = offs[n + 1], in[DI_SEG0] = nseg, in[DI_SUB0] = nsub;
+        if (hd->status != JS_OK) continue;
+        for (int t = 0; t < 8; ++t) {
+            const Huff& h = t < 4 ? hd->dc[t] : hd->ac[t - 4];
+            if (!h.present) continue;
+            unsigned char* s = hs + t * DH_SPEC;
+            s[0] = 1;
+            for (int l = 1; l <= 16; ++l) s[l] = (unsigned char)(h.maxcode[l] >= 0 ? h.maxcode[l] - h.mincode[l] + 1 : 0);
+            memcpy(s + 17, h.vals, (size_t)h.nvals);
+        }
+        for (int c = 0; c < hd->ncomp; ++c) in[DI_SEL] |= (long long)(hd->td[c] | hd->ta[c] << 4) << (8 * c);
+        rows.clear();
+        const long k = scan_segments(d, len, *hd, &rows);
+        if (k < 0) {
+            in[DI_HOST] = 1;
+            continue;
+        }
+        long subs = 0;
+        for (long i = 0; i < k; ++i) {
+            long long* r = rows.data() + i * DH_SEG;
+            const long bits = (long)(r[SG_END] - r[SG_FIRST]) * 8;
+            const long ns = bits ? (bits + DH_S - 1) / DH_S : 1;
+            if (seg) {
+                if (nseg + i >= seg_cap) {
+                    rc = DBN_ERR_ARG;
+                    break;
+                }
+                long long* o = seg + (nseg + i) * DH_SEG;
+                memcpy(o, r, sizeof(long long) * DH_SEG);
+                o[SG_IMAGE] = n, o[SG_FIRST] += offs[n], o[SG_END] += offs[n];
+                sub_base[nseg + i] = nsub + subs;
+            }
+            subs += ns;
+        }
+        const long wgs = (subs + DH_THREADS - 1) / DH_THREADS;
+        if (seg && rc == DBN_OK) {
+            if (nwg + wgs > wg_cap) rc = DBN_ERR_ARG;
+            for (long w = 0; w < wgs && rc == DBN_OK; ++w) {
+                int* o = wgtab + (nwg + w) * 4;
+                o[0] = n, o[1] = (int)(nsub + w * DH_THREADS), o[2] = (int)(subs - w * DH_THREADS < DH_THREADS ? subs - w * DH_THREADS : DH_THREADS), o[3] = 0;
+            }
+        }
+        in[DI_NSEG] = k, in[DI_NSUB] = subs;
+        nseg += k, nsub += subs, nwg += wgs;
+        if (nsub > 0x7FFFFF00L) rc = DBN_ERR_ARG;
+    }
+    delete hd;
+    if (seg && rc == DBN_OK) sub_base[nseg] = nsub;
+    counts[0] = nseg, counts[1] = nsub, counts[2] = nwg, counts[3] = co;
+    return rc;
 }
 
 }  // extern "C"

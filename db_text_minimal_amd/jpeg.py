@@ -11,6 +11,10 @@ baseline decode (pinned against Pillow / libjpeg-turbo, tests/test_jpeg_cpu.py).
   decode_coefficients(obj, device)         -> (packed, shapes) (device half)
   jpeg_collate(items)                      collate_fn for items (jpeg bytes, polys, tags): the host half in the worker;
                                            DeviceBatches.convert runs the device half
+  parse_streams(datas)                     -> JpegStreams (headers and the scans cut at their markers; no entropy decoding)
+  entropy_decode_device(streams, device)   -> JpegCoefficients on the device: Huffman decoding as gfx950 kernels
+                                           (csrc/jpeg_dhuff.hip); only the compressed bytes cross to the device
+  jpeg_stream_collate(items)               jpeg_collate with parse_streams in the worker and the Huffman stage on the device
 
 Encode behind it, in the place of the reference's imageio / Pillow writes (utils.py:225,272,280, test_ocr.py:176,210,
 ts_request.py:38-39): the decoder turned round (csrc/jpeg_enc.hip).  Colour conversion, chroma downsampling, libjpeg's
@@ -100,6 +104,7 @@ class JpegCoefficients:
     include/dbnet_hip.h.  Picklable, and pin_memory() makes it what a DataLoader with pin_memory=True hands on."""
 
     ready = None  # forward_coefficients: the event after which the pinned `coef` holds the device's result
+    host_decoded = None  # entropy_decode_device: bool [N], the images the host decoder was asked for
 
     def __init__(self, coef, desc, qtabs, status):
         self.coef, self.desc, self.qtabs, self.status = coef, desc, qtabs, status
@@ -239,16 +244,19 @@ def splice_images(packed, shapes, spliced):
     return torch.cat(parts), out_shapes
 
 
-def decode_jpeg_batch(datas, device=None, threads=MAX_THREADS, fallback=False, errors='raise'):
+def decode_jpeg_batch(datas, device=None, threads=MAX_THREADS, fallback=False, errors='raise', entropy='host'):
     """JPEG byte strings -> (packed uint8 device tensor, shapes [(H, W)]): RGB, image after image, what
     augment_images(packed, shapes, plans) takes.  A refused kind raises UnsupportedJpeg, a damaged stream CorruptJpeg (both
     name the image); fallback=True decodes refused kinds through PIL, when it is importable, and splices them in.
     errors='report': nothing raises; -> (packed, shapes, errs) with errs[i] None or the exception, a failed image taking
-    no bytes and shape (0, 0)."""
+    no bytes and shape (0, 0).  entropy='device': the Huffman stage runs on the GPU too (entropy_decode_device): only the
+    compressed bytes cross to the device; the pixels are the same."""
     if errors not in ('raise', 'report'):
         raise ValueError("errors is 'raise' or 'report'")
+    if entropy not in ('host', 'device'):
+        raise ValueError("entropy is 'host' or 'device', got %r" % (entropy, ))
     datas = list(datas)
-    obj = entropy_decode(datas, threads)
+    obj = entropy_decode(datas, threads) if entropy == 'host' else entropy_decode_device(datas, device)
     errs = obj.errors()
     spliced = {}
     if fallback:
@@ -271,9 +279,9 @@ def decode_jpeg_batch(datas, device=None, threads=MAX_THREADS, fallback=False, e
     return (packed, shapes) if errors == 'raise' else (packed, shapes, errs)
 
 
-def decode_jpeg(data, device=None, fallback=False):
+def decode_jpeg(data, device=None, fallback=False, entropy='host'):
     """one JPEG byte string -> uint8 [H, W, 3] device tensor (RGB; grey replicated)"""
-    packed, shapes = decode_jpeg_batch([data], device, 1, fallback)
+    packed, shapes = decode_jpeg_batch([data], device, 1, fallback, entropy=entropy)
     return packed.view(shapes[0][0], shapes[0][1], 3)
 
 
@@ -282,6 +290,148 @@ def jpeg_collate(items):
     (JpegCoefficients, shapes, per-image lists of fp64 [V, 2] polygons, per-image tag lists); DeviceBatches.convert runs the
     device half.  A stream that cannot be decoded raises (UnsupportedJpeg / CorruptJpeg)."""
     obj = entropy_decode([b[0] for b in items], threads=min(len(items), MAX_THREADS))
+    for e in obj.errors():
+        if e is not None:
+            raise e
+    polys = [[np.asarray(p, dtype=np.float64).reshape(-1, 2) for p in b[1]] for b in items]
+    tags = [list(b[2]) if b[2] is not None else [None] * len(b[1]) for b in items]
+    return obj, obj.shapes, polys, tags
+
+
+# ---- entropy decoding on the device ------------------------------------------------------------------------------------
+DHUFF_BITS, DHUFF_LANES = 1024, 256  # bits per subsequence, subsequences per workgroup (csrc/jpeg_dhuff.h)
+DHUFF_ROUNDS = 4  # propagation launches after the first: twice the most any surveyed stream needed (DESIGN section 26)
+_SEG, _DINFO, _SPEC = 6, 8, 273
+_DI_HOST = 1
+
+
+class JpegStreams:
+    """parse_streams' result for a batch, the input of entropy_decode_device: the streams themselves (`blob` uint8 tensor,
+    `offs` int64 [N + 1]), `desc` / `qtabs` / `status` as in JpegCoefficients (from the headers alone: what is wrong inside a
+    scan is found when it is decoded), `tables` uint8 [N, 8, 273] (Huffman table specs), `info` int64 [N, 8], `segments`
+    int64 [S, 6] = {image, first byte, end byte, first MCU, MCUs, n of the RSTn in front or -1} (one row per restart
+    interval), `sub_base` int64 [S + 1], `wgtab` int32 [G, 4] and `coef_elems`.  Layouts: include/dbnet_hip.h.  Picklable."""
+
+    def __init__(self, blob, offs, desc, qtabs, status, tables, info, segments, sub_base, wgtab, coef_elems):
+        self.blob, self.offs, self.desc, self.qtabs, self.status = blob, offs, desc, qtabs, status
+        self.tables, self.info, self.segments, self.sub_base, self.wgtab, self.coef_elems = tables, info, segments, sub_base, wgtab, int(coef_elems)
+
+    @property
+    def shapes(self):
+        return [(int(d[_D_H]), int(d[_D_W])) if s == 0 else (0, 0) for d, s in zip(self.desc, self.status)]
+
+    @property
+    def host_only(self):
+        """bool [N]: scans whose markers are not the ones the header calls for; the host decoder says what is wrong"""
+        return self.info[:, _DI_HOST] != 0
+
+    def __len__(self):
+        return len(self.status)
+
+    def pin_memory(self):
+        if not self.blob.is_pinned():
+            self.blob = self.blob.pin_memory()
+        return self
+
+    def errors(self):
+        """per image None or the JpegError its header gives"""
+        return [None if s == 0 else _error(int(s), i) for i, s in enumerate(self.status)]
+
+    def stream(self, i):
+        """the bytes of stream i"""
+        return self.blob[int(self.offs[i]):int(self.offs[i + 1])].numpy().tobytes()
+
+
+def parse_streams(datas, pin=None):
+    """Host half of the device entropy stage: the headers of the JPEG byte strings `datas` (the kinds and status codes of
+    entropy_decode) and their scans cut into restart intervals at the markers -> JpegStreams.  No bit of the entropy data
+    is read.  Runs anywhere, e.g. in a DataLoader worker.  pin: as entropy_decode."""
+    views = [_bytes_view(d) for d in datas]
+    N = len(views)
+    if N == 0:
+        raise ValueError('parse_streams needs at least one stream')
+    offs = np.zeros(N + 1, np.int64)
+    offs[1:] = np.cumsum([v.size for v in views])
+    if pin is None:
+        pin = torch.utils.data.get_worker_info() is None and torch.cuda.is_available()
+    blob = torch.empty(max(int(offs[-1]), 1), dtype=torch.uint8, pin_memory=bool(pin))
+    if offs[-1]:
+        np.concatenate(views, out=blob.numpy()[:int(offs[-1])])
+    desc, qtabs, status = np.zeros((N, _DESC), np.int64), np.zeros((N, 3, 64), np.uint16), np.zeros(N, np.int32)
+    tables, info, counts = np.zeros((N, 8, _SPEC), np.uint8), np.zeros((N, _DINFO), np.int64), np.zeros(4, np.int64)
+    L = lib()
+    head = (blob.data_ptr(), offs.ctypes.data, N, desc.ctypes.data, qtabs.ctypes.data, status.ctypes.data, tables.ctypes.data, info.ctypes.data)
+    check(L.dbn_jpeg_stream_plan(*head, None, 0, None, None, 0, counts.ctypes.data), 'jpeg_stream_plan')
+    nseg, nwg = int(counts[0]), int(counts[2])
+    seg, sub_base, wgtab = np.zeros((nseg, _SEG), np.int64), np.zeros(nseg + 1, np.int64), np.zeros((nwg, 4), np.int32)
+    one = np.zeros(8, np.int64)  # ctypes has no address for an empty array
+    check(L.dbn_jpeg_stream_plan(*head, seg.ctypes.data if nseg else one.ctypes.data, nseg, sub_base.ctypes.data,
+                                 wgtab.ctypes.data if nwg else one.ctypes.data, nwg, counts.ctypes.data), 'jpeg_stream_plan')
+    return JpegStreams(blob, offs, desc, qtabs, status, tables, info, seg, sub_base, wgtab, counts[3])
+
+
+def dhuff_workspace_bytes(streams):
+    return int(lib().dbn_jpeg_dhuff_ws_bytes(int(streams.sub_base[-1])))
+
+
+def _dhuff_launch(st, dev, rounds, coef, ws):
+    """the launches of dbn_jpeg_dhuff on the current stream of `dev` into coef (int16 [st.coef_elems]) and the workspace ws
+    (uint8) -> the result words, still on the device: uint64 [rounds + 2, N] as int64"""
+    N = len(st)
+    res = torch.empty((rounds + 2) * N, dtype=torch.int64, device=dev)
+    blob = st.blob.to(dev, non_blocking=True)
+    desc = st.desc.copy()
+    desc[:, _D_STATUS] = st.status
+    arrs = [_up(a, dev) for a in (desc, st.tables, st.info, st.segments if len(st.segments) else np.zeros((1, _SEG), np.int64), st.sub_base,
+                                  st.wgtab if len(st.wgtab) else np.zeros((1, 4), np.int32))]
+    check(lib().dbn_jpeg_dhuff(blob.data_ptr(), blob.numel(), *[a.data_ptr() for a in arrs], N, len(st.segments), int(st.sub_base[-1]), len(st.wgtab),
+                               rounds, coef.data_ptr(), st.coef_elems, ws.data_ptr(), ws.numel(), res.data_ptr(),
+                               torch.cuda.current_stream(dev).cuda_stream), 'jpeg_dhuff')
+    return res.view(rounds + 2, N)
+
+
+def entropy_decode_device(streams, device=None, max_rounds=None):
+    """entropy_decode on the device (csrc/jpeg_dhuff.hip): JpegStreams (or JPEG byte strings, parsed here) -> JpegCoefficients
+    whose `coef` is a device tensor, the same coefficients, descriptors and status.  Runs on the current stream; the host
+    waits once, for one result word per image and launch.  An image the device flagged (damaged data, markers that
+    disagree with the header) or that had not reached the fixed point after max_rounds propagation launches (default
+    DHUFF_ROUNDS) is decoded by the host decoder alone and uploaded: `host_decoded` names these images, and every status
+    is the host decoder's."""
+    st = streams if isinstance(streams, JpegStreams) else parse_streams(list(streams))
+    rounds = DHUFF_ROUNDS if max_rounds is None else int(max_rounds)
+    if not 0 <= rounds <= 64:
+        raise ValueError('max_rounds is 0 .. 64, got %r' % (max_rounds, ))
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    if dev.type != 'cuda':
+        raise ValueError('entropy_decode_device runs on a GPU device, not %s' % dev)
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    N = len(st)
+    status, desc = st.status.copy(), st.desc.copy()
+    with torch.cuda.device(dev):
+        coef = torch.empty(max(st.coef_elems, 1), dtype=torch.int16, device=dev)
+        ws = torch.empty(max(dhuff_workspace_bytes(st), 8), dtype=torch.uint8, device=dev)
+        res = _dhuff_launch(st, dev, rounds, coef, ws).cpu().numpy()  # the one wait
+        redo = (status == 0) & (st.host_only | (res[0] != -1) | (res[rounds + 1] != 0))
+        idx = np.nonzero(redo)[0]
+        if idx.size:
+            sub = entropy_decode([st.stream(i) for i in idx], pin=False)
+            for k, i in enumerate(idx):
+                o, e = int(sub.desc[k, _D_COEF]), int(desc[i, _D_COEF])
+                n = int(sub.desc[k + 1, _D_COEF]) if k + 1 < len(idx) else sub.coef.numel()
+                coef[e:e + n - o].copy_(sub.coef[o:n], non_blocking=False)
+                status[i] = sub.status[k]
+    desc[:, _D_STATUS] = status
+    obj = JpegCoefficients(coef[:st.coef_elems], desc, st.qtabs.copy(), status)
+    obj.host_decoded = redo
+    return obj
+
+
+def jpeg_stream_collate(items):
+    """jpeg_collate for the device entropy stage: the worker only parses (parse_streams) -> (JpegStreams, shapes, polys,
+    tags); DeviceBatches.convert runs the Huffman stage and the pixel stage on the device.  A header that cannot be decoded
+    raises here; a damaged scan raises in convert."""
+    obj = parse_streams([b[0] for b in items])
     for e in obj.errors():
         if e is not None:
             raise e

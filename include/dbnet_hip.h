@@ -907,6 +907,31 @@ int dbn_jpeg_huff_code(const short* coef, long coef_elems, const long long* desc
 int dbn_jpeg_huff_headers(const long long* desc, const unsigned short* qtabs, int N, int restart_interval, const unsigned short* specs, int per_image,
                           const int* status, unsigned char* out, long long* lens);
 
+/* ---- Huffman decoding on the device (csrc/jpeg_dhuff.hip; host plan in csrc/jpeg.hip; shared layouts in csrc/jpeg_dhuff.h): the coefficients
+ * of dbn_jpeg_entropy_batch from the compressed bytes in device memory, by subsequences of 1024 bits with the decoder state propagated to
+ * a fixed point.
+ * dbn_jpeg_stream_plan (host; reads no bit of the entropy data): desc / qtabs / status as dbn_jpeg_entropy_batch writes them from the headers
+ * (same kinds, same codes); hspec uint8 [N][8][273] (DC 0 .. 3, AC 0 .. 3: present, symbols per length [16], symbols [256]); info int64 [N][8] =
+ * {table ids (DC of component c in bits 8c .. 8c + 3, AC in 8c + 4 .. 8c + 7), host-only (the scan's markers are not the ones the header calls
+ * for: a missing or extra marker, a wrong RSTn, fill bytes, the end of the data), first / end byte of the stream in the blob, first segment,
+ * segments, first subsequence, subsequences}; seg int64 [segments][6] = {image, first byte, end byte (the FF of the marker behind it), first MCU,
+ * MCUs, n of the RSTn in front or -1}, one row per restart interval; sub_base int64 [segments + 1], the first subsequence of each segment over
+ * the batch; wgtab int32 [workgroups][4] = {image, first subsequence, count <= 256, 0}; counts int64 [4] = {segments, subsequences, workgroups,
+ * int16 coefficients}.  seg == NULL: counts only (call twice).
+ * dbn_jpeg_dhuff_ws_bytes: workspace for that many subsequences (two state buffers, block counts and their scan).
+ * dbn_jpeg_dhuff (device; rounds + 5 launches and three memsets, no synchronisation): everything above in device memory, desc with the status in
+ * field 22.  coef is zeroed and every planned image's slice written.  res uint64 [(rounds + 2) N]: res[n] all ones, or lowered to (subsequence
+ * << 4 | reason) when image n's data or plan rows were not followed; res[(1 + r) N + n] != 0 when propagation launch r changed a state of image
+ * n.  Image n is decoded when res[n] is all ones and res[(1 + rounds) N + n] == 0; any other image (and every host-only one) is the host
+ * decoder's, whose status is the one to report.  ws 8-byte aligned. */
+int dbn_jpeg_stream_plan(const unsigned char* blob, const long long* offs, int N, long long* desc, unsigned short* qtabs, int* status,
+                         unsigned char* hspec, long long* info, long long* seg, long seg_cap, long long* sub_base, int* wgtab, long wg_cap,
+                         long long* counts);
+long dbn_jpeg_dhuff_ws_bytes(long nsub);
+int dbn_jpeg_dhuff(const unsigned char* blob, long blob_len, const long long* desc, const unsigned char* hspec, const long long* info,
+                   const long long* seg, const long long* sub_base, const int* wgtab, int N, long nseg, long nsub, int nwg, int rounds, short* coef,
+                   long coef_elems, void* ws, long ws_bytes, unsigned long long* res, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
