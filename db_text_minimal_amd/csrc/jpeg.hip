@@ -23,14 +23,14 @@
 // chroma, DRI / RSTn, up to 4 Huffman and quantisation tables (8- or 16-bit entries), fill bytes and FF00 stuffing.  Every
 // other kind is refused with its own status code (include/dbnet_hip.h).  The parser takes untrusted bytes: every read is
 // checked against the end of the stream, and a decode writes only inside its image's slice of the coefficient buffer.
+// The descriptor's fields, the zigzag order, the canonical code ranges and the thread pool are jpeg_common.h's.
 #include <string.h>
 
-#include <atomic>
-#include <thread>
-#include <vector>
-
 #include "common.h"
+#include "jpeg_common.h"
 #include "jpeg_dhuff.h"
+
+using namespace dbn_jpeg;
 
 namespace {
 
@@ -39,14 +39,7 @@ enum {
     JS_MULTISCAN, JS_BAD_HEADER, JS_BAD_CODE, JS_COEF_RUN, JS_MARKER
 };
 
-constexpr int JP_DESC = 24;  // int64 per image, see include/dbnet_hip.h
 constexpr int JP_INFO = 24;
-// descriptor fields
-enum { D_COEF = 0, D_W, D_H, D_NC, D_OUT, D_QT, D_COMP /* 4 per component: bw, bh, h, v */, D_HMAX = 18, D_VMAX, D_MCUX, D_MCUY, D_STATUS, D_RI };
-
-const unsigned char kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                   41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                   30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 // ---- host: markers ------------------------------------------------------------------------------------------------------
 struct Huff {
@@ -76,25 +69,16 @@ struct Header {
 };
 
 bool build_huff(Huff& t, const unsigned char* counts, const unsigned char* vals, int nvals) {
+    int k;
+    if (!code_ranges(counts, t.mincode, t.maxcode, t.first, &k)) return false;
     memset(t.fast, 0, sizeof(t.fast));
     t.nvals = nvals;
     memcpy(t.vals, vals, nvals);
-    int code = 0, k = 0;
-    for (int l = 1; l <= 16; ++l) {
-        const int n = counts[l - 1];
-        if (code + n > (1 << l)) return false;
-        t.mincode[l] = code;
-        t.maxcode[l] = n ? code + n - 1 : -1;
-        t.first[l] = k;
-        if (l <= 9) {
-            for (int i = 0; i < n; ++i) {
-                const int c = (code + i) << (9 - l);
-                for (int j = 0; j < (1 << (9 - l)); ++j) t.fast[c + j] = (unsigned short)(l << 8 | vals[k + i]);
-            }
+    for (int l = 1; l <= 9; ++l)
+        for (int i = 0; i < counts[l - 1]; ++i) {
+            const int c = (t.mincode[l] + i) << (9 - l);
+            for (int j = 0; j < (1 << (9 - l)); ++j) t.fast[c + j] = (unsigned short)(l << 8 | vals[t.first[l] + i]);
         }
-        code = (code + n) << 1;
-        k += n;
-    }
     t.present = true;
     return true;
 }
@@ -444,6 +428,7 @@ struct Img {
 // A descriptor is used only if everything it makes a kernel touch lies inside the buffers: the coefficient / plane range
 // [coef, coef + blocks * 64) inside coef_elems, the tables inside qt_elems, the pixels inside out_bytes, and the grids
 // large enough for the image (the Python layer passes what dbn_jpeg_entropy_batch wrote; a failed image has status != 0).
+// Laxer than jpeg_common.h's read_scan on purpose: any grid that covers the image is taken, not only the derived one.
 __device__ __forceinline__ bool load_img(const long long* __restrict__ d, long coef_elems, long qt_elems, long out_bytes, Img& g) {
     if (d[D_STATUS] != 0) return false;
     const long long W = d[D_W], H = d[D_H], nc = d[D_NC];
@@ -706,31 +691,15 @@ int dbn_jpeg_entropy_batch(const unsigned char* blob, const long long* offs, int
         status[n] = hd.status;
         if (!describe(hd, n, coef_elems, co, oo, desc + (long)n * JP_DESC, qtabs + (long)n * 192)) return DBN_ERR_ARG;
     }
-    int T = threads < 1 ? 1 : threads;
-    T = T > 16 ? 16 : T;
-    T = T > N ? N : T;
-    std::atomic<int> next(0);
-    auto work = [&]() {
-        for (;;) {
-            const int n = next.fetch_add(1);
-            if (n >= N) return;
-            if (hds[n].status != JS_OK) continue;
-            long long* d = desc + (long)n * JP_DESC;
-            const int s = decode_scan(blob + offs[n], (long)(offs[n + 1] - offs[n]), hds[n], coef + d[D_COEF]);
-            if (s != JS_OK) {
-                memset(coef + d[D_COEF], 0, (size_t)hds[n].coef_elems() * sizeof(short));
-                d[D_STATUS] = status[n] = s;
-            }
+    on_threads(N, threads, [&](int n) {
+        if (hds[n].status != JS_OK) return;
+        long long* d = desc + (long)n * JP_DESC;
+        const int s = decode_scan(blob + offs[n], (long)(offs[n + 1] - offs[n]), hds[n], coef + d[D_COEF]);
+        if (s != JS_OK) {
+            memset(coef + d[D_COEF], 0, (size_t)hds[n].coef_elems() * sizeof(short));
+            d[D_STATUS] = status[n] = s;
         }
-    };
-    if (T == 1) {
-        work();
-    } else {
-        std::vector<std::thread> pool;
-        for (int i = 1; i < T; ++i) pool.emplace_back(work);
-        work();
-        for (auto& th : pool) th.join();
-    }
+    });
     return DBN_OK;
 }
 

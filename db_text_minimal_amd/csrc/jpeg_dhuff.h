@@ -1,4 +1,5 @@
-// What the host plan (dbn_jpeg_stream_plan, jpeg.hip) and the device Huffman decoder (jpeg_dhuff.hip) agree on.
+// What the host plan (dbn_jpeg_stream_plan, jpeg.hip) and the device Huffman decoder (jpeg_dhuff.hip) agree on: the layout of
+// the plan.  The descriptor, its checks and the canonical Huffman code ranges both use are jpeg_common.h's.
 #pragma once
 
 namespace dbn_dhuff {

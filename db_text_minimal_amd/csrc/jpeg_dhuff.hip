@@ -26,16 +26,17 @@
 // subsequence.  An image is given to the host decoder (by the caller) when its key was lowered or its last launch still
 // changed a state: the device never decides a status.  Every read is checked against the segment's end and the blob, every
 // write against the image's slice; table entries that disagree with the plan are not followed (the image is flagged).
+// The descriptor, its checked geometry (read_scan, block_at), the zigzag order and the canonical code ranges are jpeg_common.h's.
 #include "common.h"
+#include "jpeg_common.h"
 #include "jpeg_dhuff.h"
 
 using namespace dbn_dhuff;
+using namespace dbn_jpeg;
 
 namespace {
 
 typedef unsigned long long u64;
-constexpr int JP_DESC = 24;
-enum { D_COEF = 0, D_W, D_H, D_NC, D_OUT, D_QT, D_COMP, D_HMAX = 18, D_VMAX, D_MCUX, D_MCUY, D_STATUS, D_RI };
 // why an image was flagged (the low bits of its key; the host decoder gives the status that is reported)
 enum { DE_PLAN = 1, DE_CODE, DE_RUN, DE_BITS, DE_MCUS };
 #define DH_TRY(x)                                         \
@@ -45,10 +46,6 @@ enum { DE_PLAN = 1, DE_CODE, DE_RUN, DE_BITS, DE_MCUS };
     } while (0)
 constexpr int DH_CAP = DH_S + 64;  // symbols one F_i may take: each is at least one bit
 
-__device__ constexpr unsigned char kZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
 // the host reader's lookup (jpeg.hip Huff): 9-bit prefix table, min / max code per longer length
 struct Tab {
     unsigned short fast[512];
@@ -57,42 +54,9 @@ struct Tab {
     unsigned char vals[256];
 };
 
-struct Geo {
-    long long coef, off1, off2, blocks, mcus;
-    int nc, hs, vs, mcux, bpm, nl, ri;
-};
-
-// the scan geometry of a descriptor, only if it is the one its size and sampling give and its coefficients lie in the buffer
-__device__ __forceinline__ bool load_geo(const long long* __restrict__ d, long coef_elems, Geo& g) {
-    if (d[D_STATUS] != 0) return false;
-    const long long W = d[D_W], H = d[D_H], nc = d[D_NC], ri = d[D_RI];
-    if (W < 1 || H < 1 || W > 65535 || H > 65535 || (nc != 1 && nc != 3) || ri < 0 || ri > 65535) return false;
-    const long long h0 = d[D_COMP + 2], v0 = d[D_COMP + 3];
-    if (!((h0 == 1 && v0 == 1) || (nc == 3 && h0 == 2 && (v0 == 1 || v0 == 2)))) return false;
-    g.nc = (int)nc, g.hs = (int)h0, g.vs = (int)v0, g.ri = (int)ri;
-    g.mcux = (int)((W + 8 * h0 - 1) / (8 * h0));
-    const long long mcuy = (H + 8 * v0 - 1) / (8 * v0);
-    g.mcus = g.mcux * mcuy;
-    if (d[D_COMP] != g.mcux * h0 || d[D_COMP + 1] != mcuy * v0) return false;
-    for (int c = 1; c < nc; ++c)
-        if (d[D_COMP + 4 * c] != g.mcux || d[D_COMP + 4 * c + 1] != mcuy || d[D_COMP + 4 * c + 2] != 1 || d[D_COMP + 4 * c + 3] != 1) return false;
-    g.nl = nc == 3 ? (int)(h0 * v0) : 1;
-    g.bpm = nc == 3 ? g.nl + 2 : 1;
-    g.off1 = g.mcus * g.nl * 64, g.off2 = g.off1 + g.mcus * 64;
-    g.blocks = g.mcus * g.bpm;
-    g.coef = d[D_COEF];
-    return g.coef >= 0 && (g.coef & 7) == 0 && g.coef + g.blocks * 64 <= coef_elems;
-}
-
-// element offset of block j of an MCU (luma blocks row by row, then Cb, Cr); always inside [g.coef, g.coef + g.blocks * 64)
-// for 0 <= mcu < g.mcus and 0 <= j < g.bpm
-__device__ __forceinline__ long long block_at(const Geo& g, long long mcu, int j) {
-    const long long my = mcu / g.mcux, mx = mcu - my * g.mcux;
-    if (j < g.nl) {
-        const int v = j / g.hs, u = j - v * g.hs;
-        return g.coef + ((my * g.vs + v) * ((long long)g.mcux * g.hs) + mx * g.hs + u) * 64;
-    }
-    return g.coef + (j == g.nl ? g.off1 : g.off2) + mcu * 64;
+// the decoder's own conditions on a descriptor: a block is loaded as 16-byte vectors, the restart interval is one a DRI holds
+__device__ __forceinline__ bool load_desc(const long long* __restrict__ d, long coef_elems, Scan& g) {
+    return read_scan(d, coef_elems, g) && (g.coef & 7) == 0 && d[D_RI] >= 0 && d[D_RI] <= 65535;
 }
 
 // ---- the image of a workgroup: its plan rows checked, its tables in LDS -------------------------------------------------------
@@ -112,7 +76,7 @@ struct Batch {
 };
 
 struct Image {
-    Geo g;
+    Scan g;
     int n, cnt;
     long g0;  // first subsequence of the workgroup
     long long begin, end, seg0, nseg, sub0, nsub;
@@ -130,7 +94,7 @@ __device__ bool load_image(const Batch& B, Image& I) {
     bool ok = in[DI_HOST] == 0 && I.begin >= 0 && I.begin <= I.end && I.end <= B.blob_len && I.seg0 >= 0 && I.nseg >= 1 &&
               I.seg0 + I.nseg <= B.nseg && I.sub0 >= 0 && I.nsub >= 1 && I.sub0 + I.nsub <= B.nsub && I.cnt >= 1 && I.cnt <= DH_THREADS &&
               I.g0 >= I.sub0 && I.g0 + I.cnt <= I.sub0 + I.nsub && B.sub_base[I.seg0] == I.sub0 && B.sub_base[I.seg0 + I.nseg] == I.sub0 + I.nsub;
-    ok = ok && load_geo(B.desc + (long)I.n * JP_DESC, B.coef_elems, I.g);
+    ok = ok && load_desc(B.desc + (long)I.n * JP_DESC, B.coef_elems, I.g);
     if (!ok && threadIdx.x == 0) flag(B, I.n, 0, DE_PLAN);
     return ok;
 }
@@ -149,18 +113,8 @@ __device__ bool build_tables(const Batch& B, const Image& I, Tab* tabs, int* s_b
         for (int i = t; i < 512; i += DH_THREADS) T.fast[i] = 0;
         T.vals[t] = s[17 + t];
         if (t == 0) {
-            int code = 0, k = 0, bad = id > 3 || s[0] != 1;
-            T.mincode[0] = 0, T.maxcode[0] = -1, T.first[0] = 0;
-            for (int l = 1; l <= 16; ++l) {
-                const int n = s[l];
-                if (code + n > (1 << l)) bad = 1;
-                T.mincode[l] = code, T.maxcode[l] = n ? code + n - 1 : -1, T.first[l] = k;
-                code = (code + n) << 1;
-                k += n;
-            }
-            if (k > 256) bad = 1;
-            T.nvals = k;
-            if (bad) *s_bad = 1;
+            const bool prefix = code_ranges(s + 1, T.mincode, T.maxcode, T.first, &T.nvals);
+            if (id > 3 || s[0] != 1 || !prefix || T.nvals > 256) *s_bad = 1;
         }
     }
     __syncthreads();
@@ -231,7 +185,7 @@ struct NoSink {
 // so far, zigzag index, value) for every coefficient taken.  -> the state; blocks: completed; err: DE_CODE / DE_RUN met (first);
 // over: a symbol would have ended behind the segment.
 template <typename Sink>
-__device__ u64 walk(const unsigned char* __restrict__ blob, const Sub& S, const Tab* __restrict__ tabs, const Geo& g, u64 st, long long stop,
+__device__ u64 walk(const unsigned char* __restrict__ blob, const Sub& S, const Tab* __restrict__ tabs, const Scan& g, u64 st, long long stop,
                     Sink& sink, int& blocks, int& err, bool& over) {
     long long pos = (unsigned)st;
     int j = (int)(st >> 32) & 255, k = (int)(st >> 40) & 255;
@@ -401,7 +355,7 @@ __global__ void __launch_bounds__(SC_THREADS) dh_scan_kernel(const unsigned* __r
 // ---- writing -----------------------------------------------------------------------------------------------------------------
 struct CoefSink {
     short* __restrict__ coef;
-    const Geo& g;
+    const Scan& g;
     long long mcu0, base, want;
     long long at = -1, at_blk = -1;
     __device__ __forceinline__ void put(int blocks, int zz, int val) {
@@ -454,8 +408,9 @@ __global__ void __launch_bounds__(DH_THREADS) dh_dc_kernel(Batch B, short* __res
     __shared__ int s_v[DH_THREADS], s_f[DH_THREADS];
     const int n = blockIdx.x / 3, c = blockIdx.x % 3, t = threadIdx.x;
     if (n >= B.N || B.info[(long)n * DH_INFO + DI_HOST] != 0 || B.info[(long)n * DH_INFO + DI_NSUB] < 1) return;
-    Geo g;
-    if (!load_geo(B.desc + (long)n * JP_DESC, B.coef_elems, g) || c >= g.nc) return;
+    Scan g;
+    if (!load_desc(B.desc + (long)n * JP_DESC, B.coef_elems, g) || c >= g.nc) return;
+    const int ri = (int)B.desc[(long)n * JP_DESC + D_RI];
     const int bc = c == 0 ? g.nl : 1;
     const long long total = g.mcus * bc;
     int carry = 0;
@@ -468,7 +423,7 @@ __global__ void __launch_bounds__(DH_THREADS) dh_dc_kernel(Batch B, short* __res
             const int jj = (int)(q - mcu * bc);
             at = block_at(g, mcu, c == 0 ? jj : g.nl + c - 1);
             v = coef[at];
-            f = jj == 0 && (g.ri ? mcu % g.ri == 0 : mcu == 0);
+            f = jj == 0 && (ri ? mcu % ri == 0 : mcu == 0);
         }
         s_v[t] = v, s_f[t] = f;
         __syncthreads();

@@ -1,19 +1,19 @@
 // What the two halves of the JPEG encode share (jpeg_enc.hip: device forward stage and host Huffman stage; jpeg_huff.hip: the
-// device Huffman stage): the descriptor fields, the checked geometry, a Huffman table as a DHT segment holds it, and the
-// host functions that build tables and write a stream's header.
+// device Huffman stage): the status codes, the host coder's geometry, a Huffman table as a DHT segment holds it, and the host
+// functions that build tables and write a stream's header.  The descriptor and its checks are jpeg_common.h's.
 #pragma once
+
+#include "jpeg_common.h"
 
 namespace dbn_jpeg {
 
-constexpr int JP_DESC = 24;  // int64 per image, see include/dbnet_hip.h
-enum { D_COEF = 0, D_W, D_H, D_NC, D_OUT, D_QT, D_COMP /* 4 per component: bw, bh, h, v */, D_HMAX = 18, D_VMAX, D_MCUX, D_MCUY, D_STATUS, D_RI };
 enum { ES_OK = 0, ES_NO_IMAGE, ES_BAD_DESC, ES_TABLE, ES_DC_RANGE, ES_AC_RANGE, ES_NO_ROOM, ES_CODE_LENGTH };
 
 constexpr long kHeaderBytes = 704;  // SOI 2, APP0 18, 3 DQT 207, SOF0 19, 4 DHT 432, DRI 6, SOS 14, EOI 2
 // A block takes at most 9 + 11 bits of DC and 63 x (16 + 10) bits of AC: 208 bytes, every one of which may be FF and stuffed.
 constexpr long kBlockBits = 20 + 63 * 26, kBlockBytes = 416;
 
-// what the host stage needs of a descriptor, checked: grids that the size and the sampling give, coefficients inside the buffer
+// what the host stage needs of a descriptor: read_scan's result per component (walk_scan and the header index them), and the tables
 struct Geo {
     int W, H, nc, mcux, mcuy, h[3], v[3], bw[3], bh[3];
     long coef, qt, comp_off[3], blocks;

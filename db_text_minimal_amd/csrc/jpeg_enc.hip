@@ -18,11 +18,8 @@
 // rounding division by 8 q, and jccoefct.c's dummy blocks (zero AC, the DC of the previous block in MCU order).  Edges:
 // the last column is replicated at full resolution; the last row at full resolution only up to a multiple of the vertical
 // sampling factor, then the last DOWNSAMPLED row down to the block grid (what libjpeg's row-group buffering does).
+// The descriptor, its checked geometry (read_scan), the zigzag order and the thread pool are jpeg_common.h's.
 #include <string.h>
-
-#include <atomic>
-#include <thread>
-#include <vector>
 
 #include "common.h"
 #include "jpeg_enc.h"
@@ -30,10 +27,6 @@
 using namespace dbn_jpeg;
 
 namespace {
-
-const unsigned char kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                   41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                   30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 // ---- device -------------------------------------------------------------------------------------------------------------
 struct Enc {
@@ -46,33 +39,21 @@ struct Enc {
 
 // A descriptor is used only if everything it makes a kernel touch lies inside the buffers: the pixels [in, in + H * W * nc)
 // inside in_bytes, the coefficient / plane range inside coef_elems, the tables inside qt_elems, and the grids exactly the
-// ones the size and the sampling give.
+// ones the size and the sampling give (read_scan).
 __device__ __forceinline__ bool load_enc(const long long* __restrict__ d, long in_bytes, long coef_elems, long qt_elems, Enc& g) {
-    if (d[D_STATUS] != 0) return false;
-    const long long W = d[D_W], H = d[D_H], nc = d[D_NC];
-    if (W < 1 || H < 1 || W > 65535 || H > 65535 || (nc != 1 && nc != 3)) return false;
-    g.W = (int)W, g.H = (int)H, g.nc = (int)nc;
-    g.coef = d[D_COEF], g.in = d[D_OUT], g.qt = d[D_QT];
-    const long long h0 = d[D_COMP + 2], v0 = d[D_COMP + 3];
-    if (!((h0 == 1 && v0 == 1) || (nc == 3 && h0 == 2 && (v0 == 1 || v0 == 2)))) return false;
-    g.hs = (int)h0, g.vs = (int)v0;
-    g.mcux = (g.W + 8 * g.hs - 1) / (8 * g.hs), g.mcuy = (g.H + 8 * g.vs - 1) / (8 * g.vs);
-    long long blocks = 0;
+    Scan s;
+    if (!read_scan(d, coef_elems, s) || (s.coef & 63)) return false;
+    g.W = (int)d[D_W], g.H = (int)d[D_H], g.nc = s.nc, g.hs = s.hs, g.vs = s.vs, g.mcux = s.mcux, g.mcuy = s.mcuy;
+    g.coef = s.coef, g.in = d[D_OUT], g.qt = d[D_QT];
+    g.comp_off[0] = 0, g.comp_off[1] = s.off1, g.comp_off[2] = s.off2;  // of a grey image: unused (no kernel takes c >= nc)
     for (int c = 0; c < 3; ++c) {
-        g.bw[c] = g.bh[c] = g.rw[c] = g.rh[c] = 0;
-        g.comp_off[c] = blocks * 64;
-        if (c >= nc) continue;
-        const int h = c == 0 ? g.hs : 1, v = c == 0 ? g.vs : 1;
-        if (d[D_COMP + 4 * c + 2] != h || d[D_COMP + 4 * c + 3] != v) return false;
-        g.bw[c] = g.mcux * h, g.bh[c] = g.mcuy * v;
-        if (d[D_COMP + 4 * c] != g.bw[c] || d[D_COMP + 4 * c + 1] != g.bh[c]) return false;
+        const int h = c == 0 ? g.hs : 1, v = c == 0 ? g.vs : 1, on = c < g.nc;
+        g.bw[c] = on * g.mcux * h, g.bh[c] = on * g.mcuy * v;
         const int cw = c == 0 ? g.W : (g.W + g.hs - 1) / g.hs, ch = c == 0 ? g.H : (g.H + g.vs - 1) / g.vs;
-        g.rw[c] = (cw + 7) / 8, g.rh[c] = (ch + 7) / 8;
-        blocks += (long long)g.bw[c] * g.bh[c];
+        g.rw[c] = on * ((cw + 7) / 8), g.rh[c] = on * ((ch + 7) / 8);
     }
-    if (g.coef < 0 || (g.coef & 63) || g.coef + blocks * 64 > coef_elems) return false;
-    if (g.qt < 0 || (g.qt & 63) || g.qt + nc * 64 > qt_elems) return false;
-    if (g.in < 0 || g.in + W * H * nc > in_bytes) return false;
+    if (g.qt < 0 || (g.qt & 63) || g.qt + g.nc * 64 > qt_elems) return false;
+    if (g.in < 0 || g.in + (long long)g.W * g.H * g.nc > in_bytes) return false;
     return true;
 }
 
@@ -493,22 +474,16 @@ const HuffSpec* annex_k() {
 
 int load_geo(const long long* d, long coef_elems, long qt_elems, Geo& g) {
     if (d[D_STATUS] != 0) return ES_NO_IMAGE;
-    const long long W = d[D_W], H = d[D_H], nc = d[D_NC];
-    if (W < 1 || H < 1 || W > 65535 || H > 65535 || (nc != 1 && nc != 3)) return ES_BAD_DESC;
-    g.W = (int)W, g.H = (int)H, g.nc = (int)nc, g.coef = (long)d[D_COEF], g.qt = (long)d[D_QT];
-    const long long h0 = d[D_COMP + 2], v0 = d[D_COMP + 3];
-    if (!((h0 == 1 && v0 == 1) || (nc == 3 && h0 == 2 && (v0 == 1 || v0 == 2)))) return ES_BAD_DESC;
-    g.mcux = (int)((W + 8 * h0 - 1) / (8 * h0)), g.mcuy = (int)((H + 8 * v0 - 1) / (8 * v0));
-    g.blocks = 0;
-    for (int c = 0; c < (int)nc; ++c) {
-        g.h[c] = c == 0 ? (int)h0 : 1, g.v[c] = c == 0 ? (int)v0 : 1;
-        g.bw[c] = g.mcux * g.h[c], g.bh[c] = g.mcuy * g.v[c];
-        if (d[D_COMP + 4 * c] != g.bw[c] || d[D_COMP + 4 * c + 1] != g.bh[c] || d[D_COMP + 4 * c + 2] != g.h[c] || d[D_COMP + 4 * c + 3] != g.v[c])
-            return ES_BAD_DESC;
-        g.comp_off[c] = g.blocks * 64;
-        g.blocks += (long)g.bw[c] * g.bh[c];
+    Scan s;
+    if (!read_scan(d, coef_elems, s)) return ES_BAD_DESC;
+    g.W = (int)d[D_W], g.H = (int)d[D_H], g.nc = s.nc, g.mcux = s.mcux, g.mcuy = s.mcuy;
+    g.coef = (long)s.coef, g.qt = (long)d[D_QT], g.blocks = (long)s.blocks;
+    g.comp_off[0] = 0, g.comp_off[1] = (long)s.off1, g.comp_off[2] = (long)s.off2;
+    for (int c = 0; c < s.nc; ++c) {
+        g.h[c] = c == 0 ? s.hs : 1, g.v[c] = c == 0 ? s.vs : 1;
+        g.bw[c] = s.mcux * g.h[c], g.bh[c] = s.mcuy * g.v[c];
     }
-    if (g.coef < 0 || g.coef + g.blocks * 64 > coef_elems || g.qt < 0 || g.qt + nc * 64 > qt_elems) return ES_BAD_DESC;
+    if (g.qt < 0 || g.qt + s.nc * 64 > qt_elems) return ES_BAD_DESC;
     return ES_OK;
 }
 
@@ -645,31 +620,14 @@ int dbn_jpeg_encode_batch_opt(const short* coef, long coef_elems, const long lon
     DBN_REQUIRE(restart_interval >= 0 && restart_interval <= 65535 && offs[0] >= 0 && offs[N] <= out_bytes);
     for (int n = 0; n < N; ++n) DBN_REQUIRE(offs[n + 1] >= offs[n]);
     const long qt_elems = (long)N * 192;
-    int T = threads < 1 ? 1 : threads;
-    T = T > 16 ? 16 : T;
-    T = T > N ? N : T;
-    std::atomic<int> next(0);
-    auto work = [&]() {
-        for (;;) {
-            const int n = next.fetch_add(1);
-            if (n >= N) return;
-            Geo g;
-            lens[n] = 0;
-            int s = load_geo(desc + (long)n * JP_DESC, coef_elems, qt_elems, g);
-            if (s == ES_OK)
-                s = encode_image(coef, qtabs, g, restart_interval, out + offs[n], (long)(offs[n + 1] - offs[n]), lens + n, optimize != 0);
-            if (s != ES_OK) lens[n] = 0;
-            status[n] = s;
-        }
-    };
-    if (T == 1) {
-        work();
-    } else {
-        std::vector<std::thread> pool;
-        for (int i = 1; i < T; ++i) pool.emplace_back(work);
-        work();
-        for (auto& th : pool) th.join();
-    }
+    on_threads(N, threads, [&](int n) {
+        Geo g;
+        lens[n] = 0;
+        int s = load_geo(desc + (long)n * JP_DESC, coef_elems, qt_elems, g);
+        if (s == ES_OK) s = encode_image(coef, qtabs, g, restart_interval, out + offs[n], (long)(offs[n + 1] - offs[n]), lens + n, optimize != 0);
+        if (s != ES_OK) lens[n] = 0;
+        status[n] = s;
+    });
     return DBN_OK;
 }
 

@@ -25,11 +25,8 @@
 // Every address is checked against the buffer it goes into; a descriptor that disagrees with its slice is not followed (the
 // image is marked ES_BAD_DESC).  An AC coefficient of more than 10 bits or a DC difference of more than 11 is left out of the
 // code, and the image's status becomes the one the host coder gives: the first failing block in scan order decides.
+// The descriptor, its checked geometry (read_scan, block_at), the zigzag order and the thread pool are jpeg_common.h's.
 #include <string.h>
-
-#include <atomic>
-#include <thread>
-#include <vector>
 
 #include "common.h"
 #include "jpeg_enc.h"
@@ -43,49 +40,6 @@ constexpr long JH_CHUNK = 4096;  // bytes of the unstuffed stream per workgroup 
 constexpr int JH_SLOTS = 4;      // images whose histograms a workgroup keeps in LDS
 typedef unsigned long long u64;
 typedef short short8 __attribute__((ext_vector_type(8)));
-
-__device__ constexpr unsigned char kZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-struct Scan {
-    long long coef, off1, off2, blocks, mcus;
-    int nc, hs, vs, mcux, bpm;
-};
-
-// The scan geometry of a descriptor, only if it is the one its size and sampling give, its coefficients lie inside the
-// buffer and it has the number of blocks the plan gave it.
-__device__ __forceinline__ bool load_scan(const long long* __restrict__ d, long coef_elems, long long planned, Scan& g) {
-    if (d[D_STATUS] != 0) return false;
-    const long long W = d[D_W], H = d[D_H], nc = d[D_NC];
-    if (W < 1 || H < 1 || W > 65535 || H > 65535 || (nc != 1 && nc != 3)) return false;
-    const long long h0 = d[D_COMP + 2], v0 = d[D_COMP + 3];
-    if (!((h0 == 1 && v0 == 1) || (nc == 3 && h0 == 2 && (v0 == 1 || v0 == 2)))) return false;
-    g.nc = (int)nc, g.hs = (int)h0, g.vs = (int)v0;
-    g.mcux = (int)((W + 8 * h0 - 1) / (8 * h0));
-    const long long mcuy = (H + 8 * v0 - 1) / (8 * v0);
-    g.mcus = g.mcux * mcuy;
-    if (d[D_COMP] != g.mcux * h0 || d[D_COMP + 1] != mcuy * v0) return false;
-    for (int c = 1; c < nc; ++c)
-        if (d[D_COMP + 4 * c] != g.mcux || d[D_COMP + 4 * c + 1] != mcuy || d[D_COMP + 4 * c + 2] != 1 || d[D_COMP + 4 * c + 3] != 1) return false;
-    g.bpm = nc == 3 ? (int)(h0 * v0) + 2 : 1;
-    g.off1 = g.mcus * h0 * v0 * 64, g.off2 = g.off1 + g.mcus * 64;
-    g.blocks = g.mcus * g.bpm;
-    g.coef = d[D_COEF];
-    if (g.coef < 0 || (g.coef & 7) || g.coef + g.blocks * 64 > coef_elems || g.blocks != planned) return false;
-    return true;
-}
-
-// element offset of block j of an MCU (luma blocks row by row, then Cb, Cr) in the coefficient buffer
-__device__ __forceinline__ long long block_at(const Scan& g, long long mcu, int j) {
-    const long long my = mcu / g.mcux, mx = mcu - my * g.mcux;
-    const int nl = g.nc == 3 ? g.hs * g.vs : 1;
-    if (j < nl) {
-        const int v = j / g.hs, u = j - v * g.hs;
-        return g.coef + ((my * g.vs + v) * ((long long)g.mcux * g.hs) + mx * g.hs + u) * 64;
-    }
-    return g.coef + (j == nl ? g.off1 : g.off2) + mcu * 64;
-}
 
 // the image of scan block gb: the last n with blk_base[n] <= gb (images without blocks share their successor's base)
 __device__ __forceinline__ int find_image(const long long* __restrict__ blk_base, int N, long long gb) {
@@ -109,7 +63,8 @@ __device__ __forceinline__ bool locate(const long long* __restrict__ desc, int N
     if (gb >= total) return false;
     w.n = find_image(blk_base, N, gb);
     w.base = blk_base[w.n];
-    if (!load_scan(desc + (long)w.n * JP_DESC, coef_elems, blk_base[w.n + 1] - w.base, w.g)) {
+    // the kernels load a block as 16-byte vectors; the image has the number of blocks the plan gave it
+    if (!read_scan(desc + (long)w.n * JP_DESC, coef_elems, w.g) || (w.g.coef & 7) || w.g.blocks != blk_base[w.n + 1] - w.base) {
         atomicMin(errkey + w.n, (u64)ES_BAD_DESC);
         return false;
     }
@@ -130,7 +85,7 @@ __device__ __forceinline__ int nbits_dev(int v) {
 template <typename Sink>
 __device__ __forceinline__ int walk_block(const short* __restrict__ coef, const Where& w, Sink& sink) {
     const long long at = block_at(w.g, w.mcu, w.j);
-    const int nl = w.g.nc == 3 ? w.g.hs * w.g.vs : 1;
+    const int nl = w.g.nl;
     const int t = w.j < nl ? 0 : 1;
     int pred = 0;
     if (w.j > 0 && w.j < nl) pred = coef[block_at(w.g, w.mcu, w.j - 1)];
@@ -492,20 +447,6 @@ void load_specs(const unsigned short* in, HuffSpec* specs) {
         specs[t].nvals = o[16] > 256 ? 256 : o[16];
         for (int i = 0; i < 256; ++i) specs[t].vals[i] = (unsigned char)o[17 + i];
     }
-}
-
-template <typename F>
-void on_threads(int N, int threads, F f) {
-    int T = threads < 1 ? 1 : (threads > 16 ? 16 : threads);
-    T = T > N ? N : T;
-    std::atomic<int> next(0);
-    auto work = [&]() {
-        for (int n; (n = next.fetch_add(1)) < N;) f(n);
-    };
-    std::vector<std::thread> pool;
-    for (int i = 1; i < T; ++i) pool.emplace_back(work);
-    work();
-    for (auto& th : pool) th.join();
 }
 
 }  // namespace

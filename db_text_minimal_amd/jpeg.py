@@ -83,6 +83,53 @@ def _bytes_view(data):
     return a
 
 
+def _concat_streams(datas, pin):
+    """byte strings -> (uint8 tensor that holds them end to end, pinned if asked, one byte long when they are empty; int64
+    offsets [N + 1])"""
+    views = [_bytes_view(d) for d in datas]
+    offs = np.zeros(len(views) + 1, np.int64)
+    offs[1:] = np.cumsum([v.size for v in views])
+    blob = torch.empty(max(int(offs[-1]), 1), dtype=torch.uint8, pin_memory=bool(pin))
+    if offs[-1]:
+        np.concatenate(views, out=blob.numpy()[:int(offs[-1])])
+    return blob, offs
+
+
+def _pin(pin):
+    """pin=None: when a GPU is visible and this is not a DataLoader worker (a loader's pin_memory=True pins there)"""
+    return bool(torch.utils.data.get_worker_info() is None and torch.cuda.is_available() if pin is None else pin)
+
+
+def _cuda_device(who, device, default=None):
+    """`device`, else `default`, else the current GPU, as a cuda device with an index; `who`: the caller's name for the error"""
+    dev = torch.device(device) if device is not None else default
+    if dev is not None and dev.type != 'cuda':
+        raise ValueError('%s runs on a GPU device, not %s' % (who, dev))
+    return dev if dev is not None and dev.index is not None else torch.device('cuda', torch.cuda.current_device())
+
+
+def _polys_tags(items):
+    """items (_, polys, tags) -> (per-image lists of fp64 [V, 2] polygons, per-image tag lists)"""
+    polys = [[np.asarray(p, dtype=np.float64).reshape(-1, 2) for p in b[1]] for b in items]
+    tags = [list(b[2]) if b[2] is not None else [None] * len(b[1]) for b in items]
+    return polys, tags
+
+
+class _JpegBatch:
+    """what a batch's results share, from `desc` and `status`"""
+
+    @property
+    def shapes(self):
+        return [(int(d[_D_H]), int(d[_D_W])) if s == 0 else (0, 0) for d, s in zip(self.desc, self.status)]
+
+    def __len__(self):
+        return len(self.status)
+
+    def errors(self):
+        """per image None or the JpegError that describes why it was not decoded (for JpegStreams: the one its header gives)"""
+        return [None if s == 0 else _error(int(s), i) for i, s in enumerate(self.status)]
+
+
 def jpeg_info(data):
     """Markers of one stream, without decoding it: dict(width, height, components, sampling [(h, v)], restart_interval,
     orientation (Exif tag 0x0112, 0 when absent; reported, not applied), process ('baseline' / 'extended'), jfif, adobe_transform
@@ -98,7 +145,7 @@ def jpeg_info(data):
                 supported=st == 0, reason=None if st == 0 else REASONS.get(st), coefficients=int(out[15]))
 
 
-class JpegCoefficients:
+class JpegCoefficients(_JpegBatch):
     """The host half's result for a batch: `coef` int16 tensor (pinned when asked for), `desc` int64 [N, 24], `qtabs` uint16
     [N, 3, 64], `status` int32 [N] (0: decoded) and `shapes` [(H, W)] ((0, 0) for an image that failed).  Layouts:
     include/dbnet_hip.h.  Picklable, and pin_memory() makes it what a DataLoader with pin_memory=True hands on."""
@@ -120,45 +167,29 @@ class JpegCoefficients:
         self.wait()
         return dict(self.__dict__)
 
-    @property
-    def shapes(self):
-        return [(int(d[_D_H]), int(d[_D_W])) if s == 0 else (0, 0) for d, s in zip(self.desc, self.status)]
-
-    def __len__(self):
-        return len(self.status)
-
     def pin_memory(self):
         if not self.coef.is_pinned():
             self.coef = self.coef.pin_memory()
         return self
-
-    def errors(self):
-        """per image None or the JpegError that describes why it was not decoded"""
-        return [None if s == 0 else _error(int(s), i) for i, s in enumerate(self.status)]
 
 
 def entropy_decode(datas, threads=MAX_THREADS, pin=None):
     """Host half: Huffman-decode the JPEG byte strings `datas` on min(len(datas), 16, threads) threads -> JpegCoefficients.
     pin: pinned coefficient memory; default when a GPU is visible and this is not a DataLoader worker (a loader's
     pin_memory=True pins it otherwise).  A stream that fails is reported in .status and fails alone."""
-    views = [_bytes_view(d) for d in datas]
-    N = len(views)
+    blob, offs = _concat_streams(datas, False)
+    N = len(offs) - 1
     if N == 0:
         raise ValueError('entropy_decode needs at least one stream')
-    offs = np.zeros(N + 1, np.int64)
-    offs[1:] = np.cumsum([v.size for v in views])
-    blob = np.concatenate(views) if offs[-1] else np.zeros(1, np.uint8)
     L = lib()
-    total = int(L.dbn_jpeg_coef_elems(blob.ctypes.data, offs.ctypes.data, N, None))
+    total = int(L.dbn_jpeg_coef_elems(blob.data_ptr(), offs.ctypes.data, N, None))
     if total < 0:
         raise RuntimeError('libdbnet_hip: jpeg_coef_elems failed')
-    if pin is None:
-        pin = torch.utils.data.get_worker_info() is None and torch.cuda.is_available()
-    coef = torch.empty(max(total, 1), dtype=torch.int16, pin_memory=bool(pin))
+    coef = torch.empty(max(total, 1), dtype=torch.int16, pin_memory=_pin(pin))
     desc = np.zeros((N, _DESC), np.int64)
     qtabs = np.zeros((N, 3, 64), np.uint16)
     status = np.zeros(N, np.int32)
-    check(L.dbn_jpeg_entropy_batch(blob.ctypes.data, offs.ctypes.data, N, coef.data_ptr(), total, desc.ctypes.data, qtabs.ctypes.data,
+    check(L.dbn_jpeg_entropy_batch(blob.data_ptr(), offs.ctypes.data, N, coef.data_ptr(), total, desc.ctypes.data, qtabs.ctypes.data,
                                    status.ctypes.data, int(threads)), 'jpeg_entropy_batch')
     return JpegCoefficients(coef[:total], desc, qtabs, status)
 
@@ -190,11 +221,7 @@ def _up(a, dev):
 def decode_coefficients(obj, device=None):
     """Device half: JpegCoefficients -> (packed uint8 device tensor, shapes), on the current stream of `device`, no host
     sync.  Images whose status is not 0 take no bytes and have shape (0, 0) (see obj.errors())."""
-    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-    if dev.type != 'cuda':
-        raise ValueError('decode_coefficients runs on a GPU device, not %s' % dev)
-    if dev.index is None:
-        dev = torch.device('cuda', torch.cuda.current_device())
+    dev = _cuda_device('decode_coefficients', device)
     shapes = obj.shapes
     out_bytes = int(sum(h * w * 3 for h, w in shapes))
     out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
@@ -293,9 +320,7 @@ def jpeg_collate(items):
     for e in obj.errors():
         if e is not None:
             raise e
-    polys = [[np.asarray(p, dtype=np.float64).reshape(-1, 2) for p in b[1]] for b in items]
-    tags = [list(b[2]) if b[2] is not None else [None] * len(b[1]) for b in items]
-    return obj, obj.shapes, polys, tags
+    return (obj, obj.shapes) + _polys_tags(items)
 
 
 # ---- entropy decoding on the device ------------------------------------------------------------------------------------
@@ -305,7 +330,7 @@ _SEG, _DINFO, _SPEC = 6, 8, 273
 _DI_HOST = 1
 
 
-class JpegStreams:
+class JpegStreams(_JpegBatch):
     """parse_streams' result for a batch, the input of entropy_decode_device: the streams themselves (`blob` uint8 tensor,
     `offs` int64 [N + 1]), `desc` / `qtabs` / `status` as in JpegCoefficients (from the headers alone: what is wrong inside a
     scan is found when it is decoded), `tables` uint8 [N, 8, 273] (Huffman table specs), `info` int64 [N, 8], `segments`
@@ -317,25 +342,14 @@ class JpegStreams:
         self.tables, self.info, self.segments, self.sub_base, self.wgtab, self.coef_elems = tables, info, segments, sub_base, wgtab, int(coef_elems)
 
     @property
-    def shapes(self):
-        return [(int(d[_D_H]), int(d[_D_W])) if s == 0 else (0, 0) for d, s in zip(self.desc, self.status)]
-
-    @property
     def host_only(self):
         """bool [N]: scans whose markers are not the ones the header calls for; the host decoder says what is wrong"""
         return self.info[:, _DI_HOST] != 0
-
-    def __len__(self):
-        return len(self.status)
 
     def pin_memory(self):
         if not self.blob.is_pinned():
             self.blob = self.blob.pin_memory()
         return self
-
-    def errors(self):
-        """per image None or the JpegError its header gives"""
-        return [None if s == 0 else _error(int(s), i) for i, s in enumerate(self.status)]
 
     def stream(self, i):
         """the bytes of stream i"""
@@ -346,17 +360,10 @@ def parse_streams(datas, pin=None):
     """Host half of the device entropy stage: the headers of the JPEG byte strings `datas` (the kinds and status codes of
     entropy_decode) and their scans cut into restart intervals at the markers -> JpegStreams.  No bit of the entropy data
     is read.  Runs anywhere, e.g. in a DataLoader worker.  pin: as entropy_decode."""
-    views = [_bytes_view(d) for d in datas]
-    N = len(views)
+    blob, offs = _concat_streams(datas, _pin(pin))
+    N = len(offs) - 1
     if N == 0:
         raise ValueError('parse_streams needs at least one stream')
-    offs = np.zeros(N + 1, np.int64)
-    offs[1:] = np.cumsum([v.size for v in views])
-    if pin is None:
-        pin = torch.utils.data.get_worker_info() is None and torch.cuda.is_available()
-    blob = torch.empty(max(int(offs[-1]), 1), dtype=torch.uint8, pin_memory=bool(pin))
-    if offs[-1]:
-        np.concatenate(views, out=blob.numpy()[:int(offs[-1])])
     desc, qtabs, status = np.zeros((N, _DESC), np.int64), np.zeros((N, 3, 64), np.uint16), np.zeros(N, np.int32)
     tables, info, counts = np.zeros((N, 8, _SPEC), np.uint8), np.zeros((N, _DINFO), np.int64), np.zeros(4, np.int64)
     L = lib()
@@ -401,11 +408,7 @@ def entropy_decode_device(streams, device=None, max_rounds=None):
     rounds = DHUFF_ROUNDS if max_rounds is None else int(max_rounds)
     if not 0 <= rounds <= 64:
         raise ValueError('max_rounds is 0 .. 64, got %r' % (max_rounds, ))
-    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-    if dev.type != 'cuda':
-        raise ValueError('entropy_decode_device runs on a GPU device, not %s' % dev)
-    if dev.index is None:
-        dev = torch.device('cuda', torch.cuda.current_device())
+    dev = _cuda_device('entropy_decode_device', device)
     N = len(st)
     status, desc = st.status.copy(), st.desc.copy()
     with torch.cuda.device(dev):
@@ -435,9 +438,7 @@ def jpeg_stream_collate(items):
     for e in obj.errors():
         if e is not None:
             raise e
-    polys = [[np.asarray(p, dtype=np.float64).reshape(-1, 2) for p in b[1]] for b in items]
-    tags = [list(b[2]) if b[2] is not None else [None] * len(b[1]) for b in items]
-    return obj, obj.shapes, polys, tags
+    return (obj, obj.shapes) + _polys_tags(items)
 
 
 # ---- encode ----------------------------------------------------------------------------------------------------------
@@ -597,16 +598,7 @@ def forward_coefficients(images, shapes=None, quality=75, subsampling='420', qta
     host_copy=False: the coefficients stay on the device (`coef.is_cuda`; no pinned buffer, no copy), for
     entropy_encode_device and decode_coefficients."""
     tables = _tables(quality, qtables)
-    if device is not None:
-        dev = torch.device(device)
-    elif isinstance(images, torch.Tensor) and images.is_cuda:
-        dev = images.device
-    else:
-        dev = torch.device('cuda', torch.cuda.current_device())
-    if dev.type != 'cuda':
-        raise ValueError('forward_coefficients runs on a GPU device, not %s' % dev)
-    if dev.index is None:
-        dev = torch.device('cuda', torch.cuda.current_device())
+    dev = _cuda_device('forward_coefficients', device, images.device if isinstance(images, torch.Tensor) and images.is_cuda else None)
     with torch.cuda.device(dev):
         flat, items = _encode_inputs(images, shapes, dev)
         hdesc, qtabs, total, tp, tf = forward_plan(items, subsampling, tables)
@@ -674,16 +666,7 @@ def entropy_encode_device(obj, restart_interval=0, optimize=False, errors='raise
     qtabs = np.ascontiguousarray(obj.qtabs, np.uint16)
     if obj.coef.dtype != torch.int16 or desc.shape != (N, _DESC) or qtabs.shape != (N, 3, 64):
         raise ValueError('not the layout of JpegCoefficients')
-    if device is not None:
-        dev = torch.device(device)
-    elif obj.coef.is_cuda:
-        dev = obj.coef.device
-    else:
-        dev = torch.device('cuda', torch.cuda.current_device())
-    if dev.type != 'cuda':
-        raise ValueError('entropy_encode_device runs on a GPU device, not %s' % dev)
-    if dev.index is None:
-        dev = torch.device('cuda', torch.cuda.current_device())
+    dev = _cuda_device('entropy_encode_device', device, obj.coef.device if obj.coef.is_cuda else None)
     L = lib()
     blk, ivl = np.zeros(N + 1, np.int64), np.zeros(N + 1, np.int64)
     status, sizes = np.zeros(N, np.int32), np.zeros(2, np.int64)
