@@ -13,4 +13,4 @@ from .render import draw_outlines, image_views, minmax_scale_u8, overlay_heatmap
 from .recognise import AttnLabelConverter, CTCLabelConverter, greedy_decode, recognize_words, words_to_input  # noqa: F401
 from .jpeg import (CorruptJpeg, JpegCoefficients, JpegEncodeError, JpegError, JpegStreams, UnsupportedJpeg, decode_coefficients, decode_jpeg,  # noqa: F401
                    decode_jpeg_batch, encode_jpeg, encode_jpeg_batch, entropy_decode, entropy_encode, entropy_encode_device, forward_coefficients, jpeg_collate,
-                   jpeg_info, optimal_huffman_table, quant_tables, save_jpegs, entropy_decode_device, jpeg_stream_collate, parse_streams)
+                   jpeg_info, jpeg_multiscan_collate, optimal_huffman_table, quant_tables, save_jpegs, entropy_decode_device, jpeg_stream_collate, parse_streams)

@@ -32,7 +32,7 @@ import torch
 
 from ._lib import check, lib
 from .gt_maps import GT_KEYS, MEAN, make_gt_maps, plan_polygons
-from .jpeg import JpegCoefficients, JpegStreams, decode_coefficients, entropy_decode_device
+from .jpeg import JpegCoefficients, JpegStreams, decode_coefficients, entropy_decode_device, stream_orientations
 
 ROTATE = (-10.0, 10.0)  # data_loaders.py:62-66
 SCALE = (0.5, 3.0)
@@ -395,10 +395,13 @@ class DeviceBatches:
     the first element is then a JpegCoefficients and its device half runs here) into the dict fit / evaluate consume: `img` (augment_images) and the four GT_KEYS maps (make_gt_maps), on `device`.  training=True draws the
     augmentation from np.random.RandomState(seed), continued across passes; False is the letterbox, and adds `anns`
     (per image, the scaled polygons) and `ignore_tags` (per image, the GT ignore flags) as the reference's test loader
-    returns them.  gt_kwargs go to make_gt_maps (shrink_ratio, thresh_min, thresh_max, min_text_size, ignore_tags)."""
+    returns them.  orient=True: JPEG batches are decoded with their Exif orientation applied (decode_coefficients), as the
+    reference's cv2.imread does; the polygons are then those of the displayed image.  gt_kwargs go to make_gt_maps
+    (shrink_ratio, thresh_min, thresh_max, min_text_size, ignore_tags)."""
 
-    def __init__(self, loader, device, training, size=640, seed=None, mean=MEAN, **gt_kwargs):
+    def __init__(self, loader, device, training, size=640, seed=None, mean=MEAN, orient=False, **gt_kwargs):
         self.loader, self.device, self.training, self.size, self.mean = loader, torch.device(device), bool(training), int(size), mean
+        self.orient = bool(orient)
         self.rng = np.random.RandomState(seed)
         self.gt_kwargs = gt_kwargs
 
@@ -408,12 +411,14 @@ class DeviceBatches:
     def convert(self, batch):
         packed, shapes, polys, tags = batch
         if isinstance(packed, JpegStreams):  # jpeg_stream_collate: the Huffman stage on the device too
+            exif = stream_orientations([packed.blob[int(a):int(b)].numpy() for a, b in zip(packed.offs[:-1], packed.offs[1:])]) if self.orient else None
             packed = entropy_decode_device(packed, self.device)
+            packed.orientation = exif
             for e in packed.errors():
                 if e is not None:
                     raise e
         if isinstance(packed, JpegCoefficients):  # jpeg_collate: the device half of the decode
-            packed, shapes = decode_coefficients(packed, self.device)
+            packed, shapes = decode_coefficients(packed, self.device, self.orient)
         if self.training:
             plans = plan_augment(shapes, polys, self.rng, self.size)
         else:

@@ -4,13 +4,14 @@ rest — dequantisation, libjpeg's slow-integer inverse DCT, fancy chroma upsamp
 write the packed uint8 layout augment_images, crop_words and draw_outlines take (csrc/jpeg.hip).  Bit for bit libjpeg's
 baseline decode (pinned against Pillow / libjpeg-turbo, tests/test_jpeg_cpu.py).
 
-  jpeg_info(data)                          -> dict (size, components, sampling, restart interval, Exif orientation, support)
+  jpeg_info(data, multiscan)               -> dict (size, components, sampling, restart interval, Exif orientation, support)
   decode_jpeg_batch(datas, device)         -> (packed uint8 device tensor, shapes): what augment_images(packed, shapes, plans) takes
   decode_jpeg(data, device)                -> uint8 [H, W, 3] device tensor (preprocess_image, crop_words, render)
   entropy_decode(datas)                    -> JpegCoefficients (host half; runs anywhere, e.g. in a DataLoader worker)
   decode_coefficients(obj, device)         -> (packed, shapes) (device half)
   jpeg_collate(items)                      collate_fn for items (jpeg bytes, polys, tags): the host half in the worker;
                                            DeviceBatches.convert runs the device half
+  jpeg_multiscan_collate(items)            the same with multiscan=True
   parse_streams(datas)                     -> JpegStreams (headers and the scans cut at their markers; no entropy decoding)
   entropy_decode_device(streams, device)   -> JpegCoefficients on the device: Huffman decoding as gfx950 kernels
                                            (csrc/jpeg_dhuff.hip); only the compressed bytes cross to the device
@@ -31,9 +32,12 @@ tests/test_jpeg_encode_cpu.py, tests/test_jpeg_optimize_cpu.py).
   optimal_huffman_table(freq)              -> (counts [16], symbols): libjpeg's optimised table for 256 symbol counts
   encode_jpeg_batch(images, ...)           -> [bytes]; encode_jpeg(image, ...) -> bytes; save_jpegs(paths, images, ...) writes files
 
-Supported: baseline and 8-bit extended sequential Huffman streams, grey or YCbCr, 4:4:4 / 4:2:2 / 4:2:0, restart markers.
-Every other kind raises UnsupportedJpeg(reason); a damaged stream raises CorruptJpeg.  The Exif orientation is reported
-(jpeg_info(...)['orientation']) and NOT applied: PIL does not apply it either, cv2.imread does.
+Supported: baseline and 8-bit extended sequential Huffman streams, grey or YCbCr, 4:4:4 / 4:2:2 / 4:2:0, restart markers; with
+multiscan=True (entropy_decode, decode_jpeg_batch, decode_jpeg, jpeg_info) also progressive (SOF2) Huffman streams and
+sequential streams whose components come in several scans, decoded by the host entropy stage into the same coefficients
+(not by entropy='device').  Every other kind raises UnsupportedJpeg(reason); a damaged stream raises CorruptJpeg.  The Exif
+orientation is reported (jpeg_info(...)['orientation'], JpegCoefficients.orientation) and applied only with orient=True
+(decode_jpeg_batch, decode_jpeg, decode_coefficients, DeviceBatches), as cv2.imread applies it; by default, as in PIL, it is not.
 """
 import os
 
@@ -44,8 +48,9 @@ from ._lib import check, lib
 
 _DESC, _INFO = 24, 24
 _D_COEF, _D_W, _D_H, _D_NC, _D_OUT, _D_QT, _D_COMP, _D_STATUS = 0, 1, 2, 3, 4, 5, 6, 22
-IDCT_BLOCKS, RGB_PIXELS = 32, 1024  # per workgroup (csrc/jpeg.hip)
+IDCT_BLOCKS, RGB_PIXELS, ORIENT_TILE = 32, 1024, 32  # per workgroup (csrc/jpeg.hip); the oriented kernel's tile is 32 x 32 pixels
 MAX_THREADS = 16
+_MULTISCAN = 1  # flags of the _ex entry points (include/dbnet_hip.h)
 
 REASONS = {
     1: 'not a JPEG stream', 2: 'truncated stream', 3: 'progressive (SOF2) is not supported', 4: 'arithmetic coding is not supported',
@@ -55,14 +60,20 @@ REASONS = {
     9: 'non-interleaved multi-scan files are not supported', 10: 'malformed header or missing table', 11: 'invalid Huffman code',
     12: 'coefficient run past index 63', 13: 'entropy data and markers disagree (too few or too many MCUs before a marker)',
 }
-_REFUSED = (3, 4, 5, 6, 7, 8, 9)  # valid JPEG kinds this decoder does not take (another decoder can)
+# status 14 exists with multiscan=True only; REASONS stays the table of the plain entry points (tests/jpeg_ref.py restates it)
+MULTISCAN_REASONS = {14: 'scan script incomplete at the end of the image, or longer than 100 scans'}
+_REFUSED = (3, 4, 5, 6, 7, 8, 9, 14)  # valid JPEG kinds this decoder does not take (another decoder can)
+
+
+def _reason(code):
+    return REASONS.get(code) or MULTISCAN_REASONS.get(code)
 
 
 class JpegError(ValueError):
     """a stream that was not decoded: .code is the status of include/dbnet_hip.h, .index the image's place in its batch"""
 
     def __init__(self, code, index=None):
-        self.code, self.index, self.reason = int(code), index, REASONS.get(int(code), 'status %d' % code)
+        self.code, self.index, self.reason = int(code), index, _reason(int(code)) or 'status %d' % code
         ValueError.__init__(self, self.reason if index is None else 'image %d: %s' % (index, self.reason))
 
 
@@ -122,6 +133,12 @@ class _JpegBatch:
     def shapes(self):
         return [(int(d[_D_H]), int(d[_D_W])) if s == 0 else (0, 0) for d, s in zip(self.desc, self.status)]
 
+    @property
+    def oriented_shapes(self):
+        """`shapes` as they are once the Exif orientation is applied: (W, H) for tags 5 .. 8"""
+        o = getattr(self, 'orientation', None)
+        return [(w, h) if o is not None and 5 <= int(o[i]) <= 8 else (h, w) for i, (h, w) in enumerate(self.shapes)]
+
     def __len__(self):
         return len(self.status)
 
@@ -130,26 +147,34 @@ class _JpegBatch:
         return [None if s == 0 else _error(int(s), i) for i, s in enumerate(self.status)]
 
 
-def jpeg_info(data):
+def jpeg_info(data, multiscan=False):
     """Markers of one stream, without decoding it: dict(width, height, components, sampling [(h, v)], restart_interval,
-    orientation (Exif tag 0x0112, 0 when absent; reported, not applied), process ('baseline' / 'extended'), jfif, adobe_transform
-    (None without the marker), precision, status, supported, reason)."""
+    orientation (Exif tag 0x0112, 0 when absent; applied by orient=True only), process ('baseline' / 'extended'), jfif,
+    adobe_transform (None without the marker), precision, status, supported, reason).  multiscan=True: what entropy_decode(...,
+    multiscan=True) takes is `supported` (process may be 'progressive'), and `scans` counts the SOS markers (0 unless supported)."""
     a = _bytes_view(data)
     out = np.zeros(_INFO, np.int64)
     buf = a if a.size else np.zeros(1, np.uint8)
-    check(lib().dbn_jpeg_info(buf.ctypes.data, int(a.size), out.ctypes.data), 'jpeg_info')
+    if multiscan:
+        check(lib().dbn_jpeg_info_ex(buf.ctypes.data, int(a.size), _MULTISCAN, out.ctypes.data), 'jpeg_info')
+    else:
+        check(lib().dbn_jpeg_info(buf.ctypes.data, int(a.size), out.ctypes.data), 'jpeg_info')
     st, nc = int(out[0]), int(out[3])
+    more = dict(scans=int(out[19])) if multiscan else {}
     return dict(width=int(out[1]), height=int(out[2]), components=nc, sampling=[(int(out[6 + 2 * c]), int(out[7 + 2 * c])) for c in range(min(nc, 4))],
-                restart_interval=int(out[4]), orientation=int(out[5]), process={0: 'baseline', 1: 'extended'}.get(int(out[14])),
+                restart_interval=int(out[4]), orientation=int(out[5]), process={0: 'baseline', 1: 'extended', 2: 'progressive'}.get(int(out[14])),
                 jfif=bool(out[16]), adobe_transform=None if out[17] < 0 else int(out[17]), precision=int(out[18]), status=st,
-                supported=st == 0, reason=None if st == 0 else REASONS.get(st), coefficients=int(out[15]))
+                supported=st == 0, reason=None if st == 0 else _reason(st), coefficients=int(out[15]), **more)
 
 
 class JpegCoefficients(_JpegBatch):
     """The host half's result for a batch: `coef` int16 tensor (pinned when asked for), `desc` int64 [N, 24], `qtabs` uint16
-    [N, 3, 64], `status` int32 [N] (0: decoded) and `shapes` [(H, W)] ((0, 0) for an image that failed).  Layouts:
-    include/dbnet_hip.h.  Picklable, and pin_memory() makes it what a DataLoader with pin_memory=True hands on."""
+    [N, 3, 64], `status` int32 [N] (0: decoded) and `shapes` [(H, W)] ((0, 0) for an image that failed): the stored shapes.
+    `orientation` int32 [N]: the Exif tags (0 or None: none), which decode_coefficients(orient=True) applies; `oriented_shapes` are
+    the shapes after that.  Layouts: include/dbnet_hip.h.  Picklable, and pin_memory() makes it what a DataLoader with
+    pin_memory=True hands on."""
 
+    orientation = None
     ready = None  # forward_coefficients: the event after which the pinned `coef` holds the device's result
     host_decoded = None  # entropy_decode_device: bool [N], the images the host decoder was asked for
 
@@ -173,25 +198,36 @@ class JpegCoefficients(_JpegBatch):
         return self
 
 
-def entropy_decode(datas, threads=MAX_THREADS, pin=None):
+def entropy_decode(datas, threads=MAX_THREADS, pin=None, multiscan=False):
     """Host half: Huffman-decode the JPEG byte strings `datas` on min(len(datas), 16, threads) threads -> JpegCoefficients.
     pin: pinned coefficient memory; default when a GPU is visible and this is not a DataLoader worker (a loader's
-    pin_memory=True pins it otherwise).  A stream that fails is reported in .status and fails alone."""
+    pin_memory=True pins it otherwise).  A stream that fails is reported in .status and fails alone.  multiscan=True:
+    progressive (SOF2) streams and sequential streams of several scans are decoded too, into the same coefficients; every
+    other stream gives what it gives without the keyword."""
     blob, offs = _concat_streams(datas, False)
     N = len(offs) - 1
     if N == 0:
         raise ValueError('entropy_decode needs at least one stream')
     L = lib()
-    total = int(L.dbn_jpeg_coef_elems(blob.data_ptr(), offs.ctypes.data, N, None))
+    flags = _MULTISCAN if multiscan else 0
+    total = int(L.dbn_jpeg_coef_elems_ex(blob.data_ptr(), offs.ctypes.data, N, flags, None))
     if total < 0:
         raise RuntimeError('libdbnet_hip: jpeg_coef_elems failed')
     coef = torch.empty(max(total, 1), dtype=torch.int16, pin_memory=_pin(pin))
     desc = np.zeros((N, _DESC), np.int64)
     qtabs = np.zeros((N, 3, 64), np.uint16)
     status = np.zeros(N, np.int32)
-    check(L.dbn_jpeg_entropy_batch(blob.data_ptr(), offs.ctypes.data, N, coef.data_ptr(), total, desc.ctypes.data, qtabs.ctypes.data,
-                                   status.ctypes.data, int(threads)), 'jpeg_entropy_batch')
-    return JpegCoefficients(coef[:total], desc, qtabs, status)
+    orientation = np.zeros(N, np.int32)
+    check(L.dbn_jpeg_entropy_batch_ex(blob.data_ptr(), offs.ctypes.data, N, coef.data_ptr(), total, desc.ctypes.data, qtabs.ctypes.data,
+                                      status.ctypes.data, orientation.ctypes.data, int(threads), flags), 'jpeg_entropy_batch')
+    obj = JpegCoefficients(coef[:total], desc, qtabs, status)
+    obj.orientation = orientation
+    return obj
+
+
+def stream_orientations(datas):
+    """the Exif orientation tags of JPEG byte strings (0: none), from their markers alone -> int32 [N]"""
+    return np.array([jpeg_info(d)['orientation'] for d in datas], np.int32)
 
 
 def work_tables(desc, status):
@@ -213,21 +249,44 @@ def work_tables(desc, status):
     return np.concatenate(ta), np.concatenate(tb)
 
 
+def tile_table(desc, status, orientation):
+    """dbn_jpeg_pixels_ex's table of the oriented images (tag 2 .. 8, status 0): int32 [n_tile, 4] {image, tile row, tile column, 0}
+    over the 32 x 32 tiles of each ORIENTED image"""
+    tt, orientation = [], np.asarray(orientation)
+    for n in np.nonzero((np.asarray(status) == 0) & (orientation >= 2) & (orientation <= 8))[0]:
+        h, w = int(desc[n][_D_H]), int(desc[n][_D_W])
+        oh, ow = (w, h) if orientation[n] >= 5 else (h, w)
+        ty, tx = np.divmod(np.arange(-(-oh // ORIENT_TILE) * -(-ow // ORIENT_TILE), dtype=np.int32), -(-ow // ORIENT_TILE))
+        e = np.zeros((ty.size, 4), np.int32)
+        e[:, 0], e[:, 1], e[:, 2] = n, ty, tx
+        tt.append(e)
+    return np.concatenate(tt) if tt else np.zeros((0, 4), np.int32)
+
+
 def _up(a, dev):
     t = torch.from_numpy(np.ascontiguousarray(a))
     return (t.pin_memory() if torch.cuda.is_available() else t).to(dev, non_blocking=True)
 
 
-def decode_coefficients(obj, device=None):
+def decode_coefficients(obj, device=None, orient=False):
     """Device half: JpegCoefficients -> (packed uint8 device tensor, shapes), on the current stream of `device`, no host
-    sync.  Images whose status is not 0 take no bytes and have shape (0, 0) (see obj.errors())."""
+    sync.  Images whose status is not 0 take no bytes and have shape (0, 0) (see obj.errors()).  orient=True: an image whose
+    obj.orientation is 2 .. 8 is written turned as cv2.imread turns it (a tiled kernel of its own, in the same call), and
+    the shapes returned are obj.oriented_shapes."""
     dev = _cuda_device('decode_coefficients', device)
-    shapes = obj.shapes
+    tags = np.zeros(len(obj), np.int32)
+    if orient and obj.orientation is not None:
+        tags = np.where(np.asarray(obj.status) == 0, np.asarray(obj.orientation, np.int32), 0).astype(np.int32)
+        tags[(tags < 2) | (tags > 8)] = 0
+    turned = bool(tags.any())
+    shapes = obj.oriented_shapes if turned else obj.shapes
     out_bytes = int(sum(h * w * 3 for h, w in shapes))
     out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
     if out_bytes == 0:
         return out, shapes
     ta, tb = work_tables(obj.desc, obj.status)
+    if turned:
+        tb, tt = tb[tags[tb[:, 0]] == 0], tile_table(obj.desc, obj.status, tags)
     hdesc = obj.desc.copy()  # pixels of the decoded images only, packed: an image whose scan failed gives its slot up
     hdesc[:, _D_OUT] = np.concatenate([[0], np.cumsum([h * w * 3 for h, w in shapes])[:-1]])
     with torch.cuda.device(dev):
@@ -236,9 +295,15 @@ def decode_coefficients(obj, device=None):
         coef = obj.coef.to(dev, non_blocking=True)
         desc, qt, a, b = _up(hdesc, dev), _up(obj.qtabs.view(np.int16), dev), _up(ta, dev), _up(tb, dev)
         planes = torch.empty(coef.numel(), dtype=torch.uint8, device=dev)
-        check(lib().dbn_jpeg_pixels(coef.data_ptr(), coef.numel(), desc.data_ptr(), qt.data_ptr(), len(obj), a.data_ptr(), len(ta), b.data_ptr(),
-                                    len(tb), planes.data_ptr(), out.data_ptr(), out_bytes, torch.cuda.current_stream(dev).cuda_stream),
-              'jpeg_pixels')
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if turned:
+            o, t = _up(tags, dev), _up(tt, dev)
+            check(lib().dbn_jpeg_pixels_ex(coef.data_ptr(), coef.numel(), desc.data_ptr(), qt.data_ptr(), len(obj), a.data_ptr(), len(ta),
+                                           b.data_ptr() if len(tb) else None, len(tb), o.data_ptr(), t.data_ptr(), len(tt), planes.data_ptr(),
+                                           out.data_ptr(), out_bytes, stream), 'jpeg_pixels')
+        else:
+            check(lib().dbn_jpeg_pixels(coef.data_ptr(), coef.numel(), desc.data_ptr(), qt.data_ptr(), len(obj), a.data_ptr(), len(ta), b.data_ptr(),
+                                        len(tb), planes.data_ptr(), out.data_ptr(), out_bytes, stream), 'jpeg_pixels')
     return out, shapes
 
 
@@ -247,6 +312,15 @@ def _pil_rgb(data):
 
     from PIL import Image
     return np.ascontiguousarray(np.asarray(Image.open(io.BytesIO(bytes(data))).convert('RGB')))
+
+
+def orient_array(a, tag):
+    """the array [H, W, ...] turned as Exif orientation `tag` says (what cv2.imread and PIL's ImageOps.exif_transpose do)"""
+    if tag in (2, 3, 7, 8):
+        a = a[:, ::-1]
+    if tag in (3, 4, 6, 7):
+        a = a[::-1]
+    return np.ascontiguousarray(np.swapaxes(a, 0, 1) if 5 <= tag <= 8 else a)
 
 
 def splice_images(packed, shapes, spliced):
@@ -271,19 +345,29 @@ def splice_images(packed, shapes, spliced):
     return torch.cat(parts), out_shapes
 
 
-def decode_jpeg_batch(datas, device=None, threads=MAX_THREADS, fallback=False, errors='raise', entropy='host'):
+def decode_jpeg_batch(datas, device=None, threads=MAX_THREADS, fallback=False, errors='raise', entropy='host', multiscan=False, orient=False):
     """JPEG byte strings -> (packed uint8 device tensor, shapes [(H, W)]): RGB, image after image, what
     augment_images(packed, shapes, plans) takes.  A refused kind raises UnsupportedJpeg, a damaged stream CorruptJpeg (both
     name the image); fallback=True decodes refused kinds through PIL, when it is importable, and splices them in.
     errors='report': nothing raises; -> (packed, shapes, errs) with errs[i] None or the exception, a failed image taking
     no bytes and shape (0, 0).  entropy='device': the Huffman stage runs on the GPU too (entropy_decode_device): only the
-    compressed bytes cross to the device; the pixels are the same."""
+    compressed bytes cross to the device; the pixels are the same.  multiscan=True: progressive and multi-scan streams are
+    decoded by the host entropy stage instead of being refused (not with entropy='device', whose kernels do not take them).
+    orient=True: the Exif orientation is applied, as cv2.imread applies it: the shapes are (W, H) for tags 5 .. 8; both entropy
+    paths, and the PIL fallback's images too."""
     if errors not in ('raise', 'report'):
         raise ValueError("errors is 'raise' or 'report'")
     if entropy not in ('host', 'device'):
         raise ValueError("entropy is 'host' or 'device', got %r" % (entropy, ))
+    if entropy == 'device' and multiscan:
+        raise ValueError("multiscan=True is the host entropy stage's: the device Huffman decoder does not take progressive or multi-scan streams")
     datas = list(datas)
-    obj = entropy_decode(datas, threads) if entropy == 'host' else entropy_decode_device(datas, device)
+    if entropy == 'host':
+        obj = entropy_decode(datas, threads, multiscan=multiscan)
+    else:
+        obj = entropy_decode_device(datas, device)
+        if orient:
+            obj.orientation = stream_orientations(datas)
     errs = obj.errors()
     spliced = {}
     if fallback:
@@ -291,6 +375,8 @@ def decode_jpeg_batch(datas, device=None, threads=MAX_THREADS, fallback=False, e
             if isinstance(e, UnsupportedJpeg):
                 try:
                     spliced[i] = _pil_rgb(datas[i])
+                    if orient:
+                        spliced[i] = orient_array(spliced[i], int(obj.orientation[i]))
                     errs[i] = None
                 except ImportError:
                     break
@@ -300,15 +386,15 @@ def decode_jpeg_batch(datas, device=None, threads=MAX_THREADS, fallback=False, e
         for e in errs:
             if e is not None:
                 raise e
-    packed, shapes = decode_coefficients(obj, device)
+    packed, shapes = decode_coefficients(obj, device, orient)
     if spliced:
         packed, shapes = splice_images(packed, shapes, spliced)
     return (packed, shapes) if errors == 'raise' else (packed, shapes, errs)
 
 
-def decode_jpeg(data, device=None, fallback=False, entropy='host'):
-    """one JPEG byte string -> uint8 [H, W, 3] device tensor (RGB; grey replicated)"""
-    packed, shapes = decode_jpeg_batch([data], device, 1, fallback, entropy=entropy)
+def decode_jpeg(data, device=None, fallback=False, entropy='host', multiscan=False, orient=False):
+    """one JPEG byte string -> uint8 [H, W, 3] device tensor (RGB; grey replicated); multiscan, orient: as decode_jpeg_batch"""
+    packed, shapes = decode_jpeg_batch([data], device, 1, fallback, entropy=entropy, multiscan=multiscan, orient=orient)
     return packed.view(shapes[0][0], shapes[0][1], 3)
 
 
@@ -317,6 +403,16 @@ def jpeg_collate(items):
     (JpegCoefficients, shapes, per-image lists of fp64 [V, 2] polygons, per-image tag lists); DeviceBatches.convert runs the
     device half.  A stream that cannot be decoded raises (UnsupportedJpeg / CorruptJpeg)."""
     obj = entropy_decode([b[0] for b in items], threads=min(len(items), MAX_THREADS))
+    for e in obj.errors():
+        if e is not None:
+            raise e
+    return (obj, obj.shapes) + _polys_tags(items)
+
+
+def jpeg_multiscan_collate(items, multiscan=True):
+    """jpeg_collate that takes progressive and multi-scan streams as well (entropy_decode(..., multiscan=True)); the keyword
+    is there for functools.partial"""
+    obj = entropy_decode([b[0] for b in items], threads=min(len(items), MAX_THREADS), multiscan=multiscan)
     for e in obj.errors():
         if e is not None:
             raise e

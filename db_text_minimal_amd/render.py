@@ -308,13 +308,13 @@ def _is_jpeg(path):
     return path.lower().endswith(('.jpg', '.jpeg'))
 
 
-def _read_image(path):
+def _read_image(path, orient=False):
     if path.endswith('.npy'):
         img = np.load(path)
-    elif _is_jpeg(path):  # the project's own decoder; a kind it refuses (progressive, CMYK, ...) goes through PIL when that is installed
+    elif _is_jpeg(path):  # the project's own decoder, progressive and multi-scan files included; a kind it refuses (CMYK, ...) goes through PIL when that is installed
         from .jpeg import decode_jpeg
         with open(path, 'rb') as f:
-            return decode_jpeg(f.read(), fallback=True)
+            return decode_jpeg(f.read(), fallback=True, multiscan=True, orient=orient)
     else:
         from PIL import Image  # only when the suffix asks for it
         img = np.asarray(Image.open(path).convert('RGB'))
@@ -354,9 +354,10 @@ def main(argv=None):
     ap.add_argument('--box_thresh', type=float, default=0.5)
     ap.add_argument('--unclip_ratio', type=float, default=1.5)
     ap.add_argument('--alpha', type=float, default=0.6)
+    ap.add_argument('--orient', action='store_true', help='apply a JPEG file\'s Exif orientation, as cv2.imread does (default: as stored)')
     args = ap.parse_args(argv)
     dev = torch.device('cuda')
-    img = _read_image(args.image)
+    img = _read_image(args.image, args.orient)
     img = (img if isinstance(img, torch.Tensor) else torch.from_numpy(img)).to(dev)
     model = DBTextModel().to(dev)
     model.load_state_dict(torch.load(args.model_path, map_location=dev))

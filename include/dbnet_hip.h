@@ -832,7 +832,8 @@ int dbn_head_tail_bwd_t(int at, const void* xb, const void* xt, const float* wb,
  * The entropy stage runs on the host, the rest (dequantise, libjpeg's slow-integer IDCT, fancy chroma upsampling, YCbCr -> RGB) on the device.
  * Status / support codes: 0 ok, 1 not a JPEG, 2 truncated, 3 progressive (SOF2), 4 arithmetic coding, 5 lossless / hierarchical, 6 sample
  * precision not 8 bits (12-bit), 7 4-component / Adobe-transform, 8 unsupported sampling factors, 9 non-interleaved multi-scan, 10 malformed
- * header or missing table, 11 invalid Huffman code, 12 coefficient run past index 63, 13 entropy data and markers disagree.
+ * header or missing table, 11 invalid Huffman code, 12 coefficient run past index 63, 13 entropy data and markers disagree, 14 scan
+ * script incomplete or longer than 100 scans (multiscan only).
  * dbn_jpeg_info: out[24] = {status, width, height, components, restart interval, Exif orientation (0: none), h0, v0, h1, v1, h2, v2, h3, v3,
  * SOF type, int16 coefficients needed (0 unless status 0), JFIF seen, Adobe transform (-1: no marker), precision, 0...}; reads data[0 .. len) only.
  * dbn_jpeg_coef_elems: streams n = blob[offs[n] .. offs[n + 1]); per_image[n] (may be NULL) and the returned sum count int16 coefficients.
@@ -844,8 +845,25 @@ int dbn_head_tail_bwd_t(int at, const void* xb, const void* xt, const float* wb,
  * dbn_jpeg_pixels: the device stage, two launches on `stream`: packed uint8 [H][W][3] RGB per image at its output byte offset (grey replicated).
  * tab_idct int32 [n_idct][4] = {image, component, first block, 0}, one entry per 32 blocks; tab_rgb int32 [n_rgb][4] = {image, chunk of 1024
  * pixels, 0, 0}; planes: coef_elems bytes of workspace; coef and qtabs 16-byte aligned, planes 8-byte aligned.  Descriptors that would leave a
- * buffer are skipped. */
+ * buffer are skipped.
+ * The _ex forms take a flags word and the Exif orientation; with flags 0 and no oriented image they are the plain forms, which keep their
+ * results.  flags 1 (multiscan): SOF2 progressive Huffman streams and SOF0 / SOF1 streams whose components come in several scans are decoded
+ * too, into the same layout: a scan of one component walks that component's real block grid ceil(ceil(W h / hmax) / 8) x ceil(ceil(H v / vmax) / 8)
+ * (its restart interval counts blocks), a scan of several walks MCUs; blocks no scan sends stay zero; a component's quantisation table is the
+ * one in force at its first scan.  A scan header that breaks T.81's rules is status 10; status 14: the scan script is incomplete at EOI (a
+ * coefficient never sent, or not refined to Al = 0) or longer than 100 scans.  dbn_jpeg_info_ex: out[19] = scans (multiscan only), SOF type 2
+ * = progressive.  dbn_jpeg_entropy_batch_ex: orientation int [N] (may be NULL) receives every header's Exif tag.
+ * dbn_jpeg_pixels_ex: orientation int32 [N] on the device; the images whose tag is 2 .. 8 are listed by the host in tab_tile int32 [n_tile][4] =
+ * {image, tile row, tile column, 0} (32 x 32 tiles of the ORIENTED image) and not in tab_rgb, and are written turned as cv2.imread turns them,
+ * [W][H][3] for tags 5 .. 8, in the same packed layout; one more launch on `stream`.  n_rgb or n_tile may be 0. */
 int dbn_jpeg_info(const unsigned char* data, long len, long long* out);
+int dbn_jpeg_info_ex(const unsigned char* data, long len, int flags, long long* out);
+long dbn_jpeg_coef_elems_ex(const unsigned char* blob, const long long* offs, int N, int flags, long long* per_image);
+int dbn_jpeg_entropy_batch_ex(const unsigned char* blob, const long long* offs, int N, short* coef, long coef_elems, long long* desc,
+                              unsigned short* qtabs, int* status, int* orientation, int threads, int flags);
+int dbn_jpeg_pixels_ex(const short* coef, long coef_elems, const long long* desc, const unsigned short* qtabs, int N, const int* tab_idct,
+                       int n_idct, const int* tab_rgb, int n_rgb, const int* orientation, const int* tab_tile, int n_tile,
+                       unsigned char* planes, unsigned char* out, long out_bytes, void* stream);
 long dbn_jpeg_coef_elems(const unsigned char* blob, const long long* offs, int N, long long* per_image);
 int dbn_jpeg_entropy_batch(const unsigned char* blob, const long long* offs, int N, short* coef, long coef_elems, long long* desc,
                            unsigned short* qtabs, int* status, int threads);
