@@ -230,6 +230,8 @@ SIGNATURES.update({
     'dbn_stem16_conv_bn_t': 'ipppiii' + 'pp' + 'ff' + 'ppppppp' + 'p',
     'dbn_head_tail_fwd_t': 'i' + SIGNATURES['dbn_head_tail_fwd'],
     'dbn_head_tail_bwd_t': 'i' + SIGNATURES['dbn_head_tail_bwd'],
+    'dbn_head_tail_bn_bwd_ws_floats': '',
+    'dbn_head_tail_bn_bwd_t': 'ii' + 'p' * 28 + 'iiii' + 'ff' + 'pp',
 })
 LONG_RETURN = {'dbn_jpeg_coef_elems', 'dbn_jpeg_coef_elems_ex', 'dbn_jpeg_dhuff_ws_bytes', 'dbn_jpeg_encode_bound', 'dbn_greedy_decode_ws_bytes', 'dbn_det_eval_ws_bytes', 'dbn_detect_ws_bytes', 'dbn_detect_poly_ws_bytes', 'dbn_detect_poly_verts_cap', 'dbn_mfma_sustained_flops', 'dbn_conv_bn_final_group_doubles', 'dbn_maxpool_bn_backward_ws_floats', 'dbn_pw16_panel_bytes', 'dbn_stem16_panel_bytes', 'dbn_convt16_panel_bytes', 'dbn_winograd_panel_floats', 'dbn_winograd_wgrad_slab_floats', 'dbn_winograd_ws_floats', 'dbn_igemm_splitk_slab_floats', 'dbn_deform_col2im_ws_bytes', 'dbn_deform_col2im_gather_ws_bytes', 'dbn_igemm_bn_final_counters', 'dbn_igemm_bn_final_group_floats', 'dbn_igemm_panel_floats_t', 'dbn_wgrad_slab_floats_hw', 'dbn_wgrad_slab_floats', 'dbn_igemm_panel_floats', 'dbn_igemm_bf16s_panel_floats', 'dbn_db_loss_ohem_ws_bytes', 'dbn_conv_bn_ws_floats', 'dbn_pyramid_conv_ws_floats'}
 _KIND = {'p': _P, 'i': _I, 'l': _L, 'f': _F}

@@ -5,10 +5,13 @@
 //                       (/root/reference/src/modules/segmentation_head.py:28-29,35-45,77-79,106-108)
 //   dbn_head_tail_bwd   d(preds) -> gradients of the two 64-channel inputs, the two
 //                       ConvT weights and biases
+//   dbn_head_tail_bn_bwd_t  the same through the two BatchNorms in front of those ConvTs: the 64-channel gradients are formed
+//                       again inside the BatchNorm-backward apply pass instead of being stored and re-read
 //   dbn_db_loss_fwd     OHEM-BCE / masked L1 / Dice sums -> 5 losses
 //                       (/root/reference/src/losses.py:18-40,48-66,75-82,105-139)
 //   dbn_db_loss_bwd     d(losses)/d(preds)
 #include "common.h"
+#include "bn_bwd_apply.h"
 
 namespace {
 
@@ -193,7 +196,12 @@ __global__ __launch_bounds__(256) void head_tail_fwd_kernel(const void* __restri
 #else
 #define DBN_HT_OCC
 #endif
-template <int AT>
+// STORE = false (dbn_head_tail_bn_bwd_t): the two gradients are not written (dxb / dxt unused) — the partial rows are the same bits.
+// U: pixels whose loads are in flight together (1: the loop as it always was).
+#ifndef DBN_HT_SUMS_UNROLL
+#define DBN_HT_SUMS_UNROLL 2  // U of the store-free form (A/B builds: 1, 4, 8)
+#endif
+template <int AT, bool STORE = true, int U = 1>
 __global__ __launch_bounds__(256) DBN_HT_OCC void head_tail_bwd_kernel(const void* __restrict__ xb, const void* __restrict__ xt, const float* __restrict__ wb,
                                      const float* __restrict__ wt, const float* __restrict__ preds,
                                      const float* __restrict__ dpreds, const float* __restrict__ sc_b,
@@ -253,20 +261,35 @@ __global__ __launch_bounds__(256) DBN_HT_OCC void head_tail_bwd_kernel(const voi
         if (hq >= Hq) { hq -= Hq; ++n; }
         n += g_n;
     };
-    for (long px = px0; px < npx; px += gstride, advance()) {
+    // everything one pixel needs from memory: the loads of `fetch` are independent of the arithmetic of `work`, so several pixels' loads
+    // can be in flight before the first is used
+    struct Raw { float P, T, dP, dT, B, dB; f32x4 vb, vt; };
+    auto fetch = [&](long px, Raw& r) {  // the pixel the walk stands on; moves the walk on
         // lane k of every quad evaluates the (a,b) = (k>>1, k&1) position (the four quads redundantly: same cache lines, same
         // instruction count), then a quad-local DPP broadcast hands all four to every lane — no cross-lane LDS traffic
+        const int ab = q & 3;
+        const long o = (long)(2 * hq + (ab >> 1)) * W + 2 * wq + (ab & 1);
+        const float* pb = preds + n * CH * HW + o;
+        const float* db = dpreds + n * CH * HW + o;
+        r.P = pb[0], r.T = pb[HW];
+        r.dP = db[0], r.dT = db[HW];
+        r.B = r.dB = 0.f;
+        if (CH == 3) {
+            r.B = pb[2 * HW];
+            r.dB = db[2 * HW];
+        }
+        r.vb = dbn_ld4<AT>(xb, px * 16 + q);
+        r.vt = dbn_ld4<AT>(xt, px * 16 + q);
+        advance();
+    };
+    auto work = [&](long px, const Raw& r) {
         float dlb = 0.f, dlt = 0.f;
         {
-            const int ab = q & 3;
-            const long o = (long)(2 * hq + (ab >> 1)) * W + 2 * wq + (ab & 1);
-            const float* pb = preds + n * CH * HW + o;
-            const float* db = dpreds + n * CH * HW + o;
-            const float P = pb[0], T = pb[HW];
-            float dP = db[0], dT = db[HW];
+            const float P = r.P, T = r.T;
+            float dP = r.dP, dT = r.dT;
             if (CH == 3) {
-                const float B = pb[2 * HW];
-                const float gB = db[2 * HW] * kstep * B * (1.f - B);
+                const float B = r.B;
+                const float gB = r.dB * kstep * B * (1.f - B);
                 dP += gB;
                 dT -= gB;
             }
@@ -275,8 +298,8 @@ __global__ __launch_bounds__(256) DBN_HT_OCC void head_tail_bwd_kernel(const voi
         }
         const f32x4 lb = {quad_bcast<0>(dlb), quad_bcast<1>(dlb), quad_bcast<2>(dlb), quad_bcast<3>(dlb)};
         const f32x4 lt = {quad_bcast<0>(dlt), quad_bcast<1>(dlt), quad_bcast<2>(dlt), quad_bcast<3>(dlt)};
-        f32x4 vb = dbn_ld4<AT>(xb, px * 16 + q);
-        f32x4 vt = dbn_ld4<AT>(xt, px * 16 + q);
+        f32x4 vb = r.vb;
+        f32x4 vt = r.vt;
         const f32x4 yb = vb, yt = vt;
         if (bn) {
 #pragma unroll
@@ -293,14 +316,21 @@ __global__ __launch_bounds__(256) DBN_HT_OCC void head_tail_bwd_kernel(const voi
             awb[e] += vb[e] * lb;
             awt[e] += vt[e] * lt;
         }
-        dbn_st4<AT>(dxb, px * 16 + q, gb);
-        dbn_st4<AT>(dxt, px * 16 + q, gt);
+        if constexpr (STORE) {
+            dbn_st4<AT>(dxb, px * 16 + q, gb);
+            dbn_st4<AT>(dxt, px * 16 + q, gt);
+        }
         if (bnsum) {
             if constexpr (AT != 0) {  // the BatchNorm backward's apply pass will read the ROUNDED gradient: sum exactly that
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    gb[e] = AT == 1 ? (float)(__bf16)gb[e] : (float)(_Float16)gb[e];
-                    gt[e] = AT == 1 ? (float)(__bf16)gt[e] : (float)(_Float16)gt[e];
+                    float fb = gb[e], ft = gt[e];
+                    if constexpr (!STORE) {  // (no store pins the fp32 value: keep the conversion apart from the last add, as HeadGradRecomputed does)
+                        asm("" : "+v"(fb));
+                        asm("" : "+v"(ft));
+                    }
+                    gb[e] = AT == 1 ? (float)(__bf16)fb : (float)(_Float16)fb;
+                    gt[e] = AT == 1 ? (float)(__bf16)ft : (float)(_Float16)ft;
                 }
             }
 #pragma unroll
@@ -316,6 +346,24 @@ __global__ __launch_bounds__(256) DBN_HT_OCC void head_tail_bwd_kernel(const voi
             abb += lb[0] + lb[1] + lb[2] + lb[3];
             abt += lt[0] + lt[1] + lt[2] + lt[3];
         }
+    };
+    // The pixels of a lane in ascending order, each added once: the sums are the same bits for every U.  U > 1: U pixels' loads issued
+    // before the first is used — at two waves per SIMD (174 VGPRs) one pixel per wave in flight left the kernel waiting on
+    // memory latency, not on HBM bandwidth (measured without the stores: 996 MB in 0.36 ms = 2.7 TB/s)
+    long px = px0;
+    if constexpr (U > 1) {
+        for (; px + (U - 1) * gstride < npx; px += U * gstride) {
+            Raw r[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) fetch(px + u * gstride, r[u]);
+#pragma unroll
+            for (int u = 0; u < U; ++u) work(px + u * gstride, r[u]);
+        }
+    }
+    for (; px < npx; px += gstride) {
+        Raw r;
+        fetch(px, r);
+        work(px, r);
     }
 #if DBN_HT_CHECK
     // A/B build (tools/cotenancy_diff.py): do the loop-invariant registers still hold what was loaded into them?  Counts, behind the partial
@@ -398,6 +446,128 @@ __global__ void fold_head_grads_kernel(const float* __restrict__ part, int nb, f
     const int j = i < 257 ? i : i - 257;
     float* dst = i < 257 ? (j < 256 ? dw_b + j : dbias_b) : (j < 256 ? dw_t + j : dbias_t);
     *dst = (float)(s * scale);
+}
+
+// Gradient source of bn_bwd_apply_body (bn_bwd_apply.h) for the BatchNorm in front of ONE branch's last ConvT: the gradient of the
+// ConvT's 64-channel input is formed again from the maps — per item the branch's four logit gradients of the pixel's 2 x 2 block
+// (the expressions of head_tail_bwd_kernel: lane k of every quad evaluates position k, a quad broadcast hands all four to every
+// lane) and w[c][0] l[0] + ... + w[c][3] l[3] for the item's channels, in head_tail_bwd_kernel's order, rounded to the storage type
+// as the stored tensor was.  br: 0 binarize (P, dP + gB), 1 thresh (T, dT - gB).
+// The body's items are 16 / QW lanes per pixel at consecutive threads, so a quad never straddles two pixels; the pixel of item i is
+// i / cin, walked with carries from the thread's first item (no division per item, see head_tail_fwd_kernel).
+template <int AT, int QW>
+struct HeadGradRecomputed {
+    struct Raw { float p, d, B, dB; };
+    const float* __restrict__ preds;
+    const float* __restrict__ dpreds;
+    f32x4 w[4 * QW];  // [channel of the item][ab]
+    long n, HW, plane;
+    int hq, wq, Hq, Wq, W, CH, br, ab;
+    long g_n;
+    int g_h, g_w;
+    float kstep;
+    __device__ __forceinline__ HeadGradRecomputed(const float* __restrict__ preds_, const float* __restrict__ dpreds_, const float* __restrict__ wgt,
+                                                  int br_, int Hq_, int Wq_, int CH_, float kstep_)
+        : preds(preds_), dpreds(dpreds_), Hq(Hq_), Wq(Wq_), CH(CH_), br(br_), kstep(kstep_) {
+        constexpr int cin = 16 / QW;
+        const long i0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
+        const long gstride = (long)gridDim.x * blockDim.x / cin;  // pixels between a thread's items (the grid is a multiple of cin / gcd(cin, 256))
+        const int c = (int)(i0 % cin) * 4 * QW;
+#pragma unroll
+        for (int e = 0; e < 4 * QW; ++e) w[e] = *reinterpret_cast<const f32x4*>(wgt + (c + e) * 4);
+        W = 2 * Wq;
+        HW = (long)(2 * Hq) * W;
+        plane = br * HW;
+        ab = threadIdx.x & 3;
+        const long px0 = i0 / cin, HWq = (long)Hq * Wq;
+        n = px0 / HWq;
+        hq = (int)((px0 - n * HWq) / Wq);
+        wq = (int)((px0 - n * HWq) - (long)hq * Wq);
+        g_n = gstride / HWq;
+        g_h = (int)((gstride - g_n * HWq) / Wq);
+        g_w = (int)((gstride - g_n * HWq) - (long)g_h * Wq);
+    }
+    __device__ __forceinline__ void fetch(long, Raw& r) {
+        const long o = (long)(2 * hq + (ab >> 1)) * W + 2 * wq + (ab & 1);
+        const float* pb = preds + n * CH * HW + o;
+        const float* db = dpreds + n * CH * HW + o;
+        r.p = pb[plane];
+        r.d = db[plane];
+        r.B = r.dB = 0.f;
+        if (CH == 3) {
+            r.B = pb[2 * HW];
+            r.dB = db[2 * HW];
+        }
+        wq += g_w;
+        if (wq >= Wq) { wq -= Wq; ++hq; }
+        hq += g_h;
+        if (hq >= Hq) { hq -= Hq; ++n; }
+        n += g_n;
+    }
+    __device__ __forceinline__ void grad(const Raw& r, f32x4 (&g)[QW]) const {
+        float d = r.d;
+        if (CH == 3) {
+            const float gB = r.dB * kstep * r.B * (1.f - r.B);
+            if (br) d -= gB;
+            else d += gB;
+        }
+        const float dl = d * r.p * (1.f - r.p);
+        const f32x4 l = {quad_bcast<0>(dl), quad_bcast<1>(dl), quad_bcast<2>(dl), quad_bcast<3>(dl)};
+#pragma unroll
+        for (int q = 0; q < QW; ++q)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float t = w[4 * q + e][0] * l[0] + w[4 * q + e][1] * l[1] + w[4 * q + e][2] * l[2] + w[4 * q + e][3] * l[3];
+                // 16-bit storage: the stored tensor held the fp32 sum rounded ONCE MORE; the empty asm keeps the conversion from fusing
+                // with the last add into one rounding (v_fma_mix*, see bn_bwd_apply_body)
+                if constexpr (AT != 0) asm("" : "+v"(t));
+                g[q][e] = round_to_storage<AT>(t);
+            }
+    }
+};
+
+struct HeadBnBranch {  // one branch's operands of head_bn_bwd_apply_kernel
+    const void* y;     // [npx][64] ConvT output = BatchNorm input
+    const float *scale, *shift, *mean, *rstd, *gamma, *c1, *c2;
+    const float* w;    // [64][4] weight of the last ConvT
+    void* dy;
+    float* bias_part;  // [64][gridDim.x] or null
+};
+
+// BatchNorm-backward apply of both branches (blockIdx.y) with the recomputed gradient; per branch exactly bn_bwd_apply_kernel's grid,
+// item mapping and arithmetic
+template <int AT, int QW>
+__global__ __launch_bounds__(256) void head_bn_bwd_apply_kernel(HeadBnBranch b0, HeadBnBranch b1, const float* __restrict__ preds,
+                                                                const float* __restrict__ dpreds, int Hq, int Wq, int CH, float kstep,
+                                                                long total) {
+    const int br = blockIdx.y;
+    const HeadBnBranch b = br ? b1 : b0;
+    HeadGradRecomputed<AT, QW> src(preds, dpreds, b.w, br, Hq, Wq, CH, kstep);
+    bn_bwd_apply_body<AT, QW>(b.y, nullptr, b.scale, b.shift, src, b.mean, b.rstd, b.gamma, b.c1, b.c2, b.dy, nullptr, 0, total, 64, b.bias_part);
+}
+
+// bn_bwd_finalize_kernel's arithmetic (pointwise.hip) for both 64-channel BatchNorms from the FOLDED sums [s1_b | s2_b | s1_t | s2_t]:
+// out = [dgamma, dbeta][2 branches] given separately, cc = [c1_b | c2_b | c1_t | c2_t]
+__global__ void head_bn_bwd_finalize_kernel(const float* __restrict__ sums, int M, float* __restrict__ dgamma_b, float* __restrict__ dbeta_b,
+                                            float* __restrict__ dgamma_t, float* __restrict__ dbeta_t, float* __restrict__ cc, float gscale) {
+    const int i = threadIdx.x;
+    if (i >= 128) return;
+    const int br = i >> 6, c = i & 63;
+    const double s1 = (double)sums[br * 128 + c], s2 = (double)sums[br * 128 + 64 + c];
+    (br ? dbeta_t : dbeta_b)[c] = (float)(s1 * gscale);
+    (br ? dgamma_t : dgamma_b)[c] = (float)(s2 * gscale);
+    cc[br * 128 + c] = (float)(s1 / M);
+    cc[br * 128 + 64 + c] = (float)(s2 / M);
+}
+
+// (pointwise.hip's fold_partials_kernel: the bias gradients of both branches' first ConvT, rows [64 b][64 t] of `nb` partials each)
+__global__ void fold_head_bias_kernel(const float* __restrict__ part_b, const float* __restrict__ part_t, int nb, float* __restrict__ out_b,
+                                      float* __restrict__ out_t, float scale) {
+    const int i = blockIdx.x * 8 + (threadIdx.x >> 5);
+    const int l32 = threadIdx.x & 31;
+    if (i >= 128) return;
+    const double s = dbn_team32_fold(i < 64 ? part_b : part_t, nb, i & 63, l32);
+    if (l32 == 0) (i < 64 ? out_b : out_t)[i & 63] = (float)(s * scale);
 }
 
 // ----------------------------------------------------------------------------------
@@ -951,6 +1121,67 @@ int dbn_head_tail_bwd(const float* xb, const float* xt, const float* wb, const f
     return dbn_head_tail_bwd_t(0, xb, xt, wb, wt, preds, dpreds, bn_scale_b, bn_shift_b, bn_scale_t, bn_shift_t, bn_mean_b, bn_rstd_b,
                                bn_mean_t, bn_rstd_t, bn_sums, dxb, dxt, dw_b, dbias_b, dw_t, dbias_t, N, Hq, Wq, channels, kstep,
                                grad_scale, ws, stream);
+}
+
+// The head-tail backward THROUGH the train-mode BatchNorm + ReLU in front of each branch's last ConvT: what dbn_head_tail_bwd_t (with
+// bn_sums) followed by one dbn_bn_backward_t per branch (sums given, recomputed ReLU mask, dbias_conv) computes, bit for bit, without
+// the two [npx][64] gradients in between ever reaching memory:
+//   1. head_tail_bwd_kernel<AT, false>: the same partial rows (weight / bias gradients of the last ConvTs, the four BatchNorm sums), no stores
+//   2. the same folds; 3. bn_bwd_finalize_kernel's arithmetic for both BatchNorms in one launch
+//   4. bn_bwd_apply_body per branch (grid.y) with the gradient formed again from the maps; 5. the fold of its bias partials
+// yb / yt: the BatchNorm inputs (= ConvT outputs) [npx][64] in the storage type; dyb / dyt: their gradients (same type);
+// dbias_conv_b / _t: optional [64] (both or neither), column sums of dyb / dyt times grad_scale.
+// phases: 3 the whole; 1 (steps 1-3) then 2 (steps 4-5) with the same arguments and workspace: the same launches as two calls, for a
+// caller that brackets the sums pass and the apply pass separately (the engine's profiler).
+static const long HEAD_BN_WS_SUMS = 2048L * (2 * 257 + 4 * 64), HEAD_BN_WS_CC = HEAD_BN_WS_SUMS + 256, HEAD_BN_WS_BIAS = HEAD_BN_WS_CC + 256;
+int dbn_head_tail_bn_bwd_ws_floats() { return (int)(HEAD_BN_WS_BIAS + 2L * 64 * STREAM_BLOCKS); }
+
+int dbn_head_tail_bn_bwd_t(int at, int phases, const void* yb, const void* yt, const float* wb, const float* wt, const float* preds, const float* dpreds,
+                           const float* bn_scale_b, const float* bn_shift_b, const float* bn_scale_t, const float* bn_shift_t,
+                           const float* bn_mean_b, const float* bn_rstd_b, const float* bn_mean_t, const float* bn_rstd_t,
+                           const float* bn_gamma_b, const float* bn_gamma_t, void* dyb, void* dyt, float* dgamma_b, float* dbeta_b,
+                           float* dgamma_t, float* dbeta_t, float* dbias_conv_b, float* dbias_conv_t, float* dw_b, float* dbias_b, float* dw_t,
+                           float* dbias_t, int N, int Hq, int Wq, int channels, float kstep, float grad_scale, float* ws, void* stream) {
+    DBN_REQUIRE(yb && yt && wb && wt && preds && dpreds && dyb && dyt && dw_b && dbias_b && dw_t && dbias_t && ws);
+    DBN_REQUIRE(bn_scale_b && bn_shift_b && bn_scale_t && bn_shift_t && bn_mean_b && bn_rstd_b && bn_mean_t && bn_rstd_t && bn_gamma_b && bn_gamma_t);
+    DBN_REQUIRE(dgamma_b && dbeta_b && dgamma_t && dbeta_t && (dbias_conv_b == nullptr) == (dbias_conv_t == nullptr));
+    DBN_REQUIRE((channels == 2 || channels == 3) && N > 0 && Hq > 0 && Wq > 0 && (long)N * Hq * Wq <= 0x7fffffffL);
+    DBN_REQUIRE(phases >= 1 && phases <= 3 && at >= 0 && at <= 2);
+    hipStream_t st = (hipStream_t)stream;
+    const long npx = (long)N * Hq * Wq;
+    const int nb = dbn_grid(npx * 16, 256, 2047);  // as dbn_head_tail_bwd_t
+    float* sums = ws + HEAD_BN_WS_SUMS;
+    float* cc = ws + HEAD_BN_WS_CC;
+    if (phases & 1) {
+        DBN_DISPATCH_AT(at, hipLaunchKernelGGL((head_tail_bwd_kernel<AT, false, DBN_HT_SUMS_UNROLL>), dim3(nb), dim3(256), 0, st, yb, yt, wb, wt, preds, dpreds, bn_scale_b,
+                                               bn_shift_b, bn_scale_t, bn_shift_t, bn_mean_b, bn_rstd_b, bn_mean_t, bn_rstd_t, (void*)nullptr,
+                                               (void*)nullptr, ws, N, Hq, Wq, channels, kstep));
+        hipLaunchKernelGGL(fold_head_grads_kernel, dim3(dbn_ceil_div(2 * 257, 8)), dim3(256), 0, st, ws, nb, dw_b, dbias_b, dw_t, dbias_t,
+                           grad_scale);
+        hipLaunchKernelGGL(fold_partials_d_kernel, dim3(dbn_ceil_div(256, 8)), dim3(256), 0, st, ws + (long)514 * nb, nb, 256, sums, 1.0f);
+        hipLaunchKernelGGL(head_bn_bwd_finalize_kernel, dim3(1), dim3(128), 0, st, sums, (int)npx, dgamma_b, dbeta_b, dgamma_t, dbeta_t, cc, grad_scale);
+    }
+    if (!(phases & 2)) return dbn_status();
+    // the apply pass as dbn_bn_backward_t launches it for C = 64: eight channels per item on 16-bit storage, four on fp32
+    const int qw = at == 0 ? 1 : 2;
+    const long total = npx * (16 / qw);
+    const int grid = bn_stream_grid(total, 64 / qw);
+    DBN_REQUIRE(grid <= STREAM_BLOCKS);
+    const bool bias = dbias_conv_b != nullptr;
+    float* bias_part = ws + HEAD_BN_WS_BIAS;
+    const HeadBnBranch b0 = {yb, bn_scale_b, bn_shift_b, bn_mean_b, bn_rstd_b, bn_gamma_b, cc, cc + 64, wb, dyb, bias ? bias_part : nullptr};
+    const HeadBnBranch b1 = {yt, bn_scale_t, bn_shift_t, bn_mean_t, bn_rstd_t, bn_gamma_t, cc + 128, cc + 192, wt, dyt,
+                             bias ? bias_part + 64L * grid : nullptr};
+    if (at == 0)
+        hipLaunchKernelGGL((head_bn_bwd_apply_kernel<0, 1>), dim3(grid, 2), dim3(256), 0, st, b0, b1, preds, dpreds, Hq, Wq, channels, kstep, total);
+    else if (at == 1)
+        hipLaunchKernelGGL((head_bn_bwd_apply_kernel<1, 2>), dim3(grid, 2), dim3(256), 0, st, b0, b1, preds, dpreds, Hq, Wq, channels, kstep, total);
+    else
+        hipLaunchKernelGGL((head_bn_bwd_apply_kernel<2, 2>), dim3(grid, 2), dim3(256), 0, st, b0, b1, preds, dpreds, Hq, Wq, channels, kstep, total);
+    if (bias)
+        hipLaunchKernelGGL(fold_head_bias_kernel, dim3(dbn_ceil_div(128, 8)), dim3(256), 0, st, bias_part, bias_part + 64L * grid, grid, dbias_conv_b,
+                           dbias_conv_t, grad_scale);
+    return dbn_status();
 }
 
 // [1024][NSUM] partial sums (doubles) + the arrival counter of the in-kernel finalize.  The caller's workspace needs NO

@@ -1831,6 +1831,74 @@ class Engine:
         return z
 
     # ----------------------------------------------------------------- backward
+    # The head tail's backward and the BatchNorm backward in front of each branch's last ConvT as ONE native call
+    # (dbn_head_tail_bn_bwd_t): the two 64-channel gradients at half resolution between them (`binarize/dz1`, `thresh/dz1`) are formed
+    # again inside the BatchNorm apply pass and are neither allocated, written nor read.  Same bits as the unfused sequence
+    # (tests/test_head_bn_bwd_gpu.py); DBN_HEAD_BWD_FUSED=0: the unfused sequence (the A/B switch).
+    head_bwd_fused = os.environ.get('DBN_HEAD_BWD_FUSED', '1') == '1'
+    head_bwd_fused_ats = (0, 1, 2)  # storage types that take the fused path (the bit-identity test runs over exactly these)
+
+    def _head_tail_args(self, out, dpreds):
+        B, head = self.bufs, self.model.segmentation_head
+        hb, ht = 'segmentation_head.binarize.4', 'segmentation_head.thresh.4'
+        return (B['binarize/y1'].data_ptr(), B['thresh/y1'].data_ptr(), head.binarize[6].weight.data_ptr(), head.thresh[6].weight.data_ptr(),
+                out.data_ptr(), dpreds.data_ptr(), B[hb + '/scale'].data_ptr(), B[hb + '/shift'].data_ptr(), B[ht + '/scale'].data_ptr(),
+                B[ht + '/shift'].data_ptr(), B[hb + '/mean'].data_ptr(), B[hb + '/rstd'].data_ptr(), B[ht + '/mean'].data_ptr(),
+                B[ht + '/rstd'].data_ptr())
+
+    def _head_tail_grads(self):
+        G = self.grad_views
+        return tuple(G['segmentation_head.%s.6.%s' % (br, k)].data_ptr() for br in ('binarize', 'thresh') for k in ('weight', 'bias'))
+
+    def _head_tail_bwd(self, out, dpreds, N, Hh, Wh):
+        """The unfused head tail: writes both 64-channel gradients and the sums of the two BatchNorm backwards that consume them;
+        returns (dz1 binarize, dz1 thresh, bn_sums [4][64])."""
+        L, head = self.L, self.model.segmentation_head
+        dz1b = self.buf('binarize/dz1', N, Hh, Wh, 64)
+        dz1t = self.buf('thresh/dz1', N, Hh, Wh, 64)
+        ws = self.scratch('_head_ws', L.dbn_head_tail_bwd_ws_floats())
+        bn_sums = self.fbuf('head/bn4_sums', 4, 64)  # the kernel also reduces what the two BatchNorm backwards need
+        # reads both 64-channel ConvT outputs, the maps and their gradients; writes both 64-channel gradients
+        self._prof_hbm('head_tail_bwd_kernel + fold_head_grads_kernel + fold_partials_d_kernel', 4.0 * dz1b.element_size() * dz1b.numel() + 4.0 * (out.numel() + dpreds.numel()))
+        check(L.dbn_head_tail_bwd_t(self.at, *self._head_tail_args(out, dpreds), bn_sums.data_ptr(), dz1b.data_ptr(), dz1t.data_ptr(),
+                                    *self._head_tail_grads(), N, Hh, Wh, 3, float(head.k), self.grad_scale, ws.data_ptr(), self.stream),
+              'head_tail_bwd')
+        if self.prof:
+            self.prof.end()
+        return dz1b, dz1t, bn_sums
+
+    def _head_tail_bn_bwd(self, out, dpreds, N, Hh, Wh):
+        """The fused head tail (see head_bwd_fused); returns (dy1 binarize, dy1 thresh), the gradients of the two ConvT outputs."""
+        L, B, G, head = self.L, self.bufs, self.grad_views, self.model.segmentation_head
+        y1b, y1t = B['binarize/y1'], B['thresh/y1']
+        dyb, dyt = self.buf('binarize/dy1', *y1b.shape), self.buf('thresh/dy1', *y1t.shape)
+        ws = self.scratch('_head_bn_ws', L.dbn_head_tail_bn_bwd_ws_floats())
+        hp = ['segmentation_head.%s.' % br for br in ('binarize', 'thresh')]
+        dbias = [None, None]
+        biased = [getattr(head, br)[3].bias is not None for br in ('binarize', 'thresh')]
+        if all(biased) and self.bias_grad_in_bn:  # (as bn_backward: 256 % (64 / 4) == 0)
+            for i in (0, 1):
+                dbias[i] = G[hp[i] + '3.bias'].data_ptr()
+                self._bias_done.add(hp[i] + '3.bias')
+        T, maps = y1b.numel() * y1b.element_size(), 4.0 * (out.numel() + dpreds.numel())
+        args = (*self._head_tail_args(out, dpreds), self.views[hp[0] + '4.weight'].data_ptr(), self.views[hp[1] + '4.weight'].data_ptr(),
+                dyb.data_ptr(), dyt.data_ptr(), G[hp[0] + '4.weight'].data_ptr(), G[hp[0] + '4.bias'].data_ptr(),
+                G[hp[1] + '4.weight'].data_ptr(), G[hp[1] + '4.bias'].data_ptr(), dbias[0], dbias[1], *self._head_tail_grads(), N, Hh, Wh, 3,
+                float(head.k), self.grad_scale, ws.data_ptr(), self.stream)
+        # the sums pass: reads both 64-channel ConvT outputs, the maps and their gradients; writes nothing large
+        self._prof_hbm('head_tail_bwd_kernel + fold_head_grads_kernel + fold_partials_d_kernel', 2.0 * T + maps, 'sums only')
+        check(L.dbn_head_tail_bn_bwd_t(self.at, 1, *args), 'head_tail_bn_bwd (sums)')
+        if self.prof:
+            self.prof.end()
+        # the apply pass of both branches: reads both ConvT outputs and, per branch, 4 of the 6 planes of the maps and their gradients;
+        # writes both gradients
+        self._prof_hbm('bn_bwd_reduce_kernel + bn_bwd_finalize_kernel + bn_bwd_apply_kernel', 4.0 * T + maps * 8.0 / 6.0,
+                       'segmentation_head.{binarize,thresh}.4 [recomputed gradient]')
+        check(L.dbn_head_tail_bn_bwd_t(self.at, 2, *args), 'head_tail_bn_bwd (apply)')
+        if self.prof:
+            self.prof.end()
+        return dyb, dyt
+
     def backward(self, dpreds):
         """Consumes d(loss)/d(preds) [N,3,H,W]; fills the flat gradient buffer."""
         if self.saved_generation != self.generation:
@@ -1852,40 +1920,31 @@ class Engine:
             check(L.dbn_bilinear_bwd(dpreds.data_ptr(), dhead.data_ptr(), N * 3, 2 * Hh, 2 * Wh, H, W, st), 'bilinear_bwd')
             dpreds = dhead
         head = m.segmentation_head
-        b6, t6 = head.binarize[6], head.thresh[6]
-        dz1b = self.buf('binarize/dz1', N, Hh, Wh, 64)
-        dz1t = self.buf('thresh/dz1', N, Hh, Wh, 64)
-        ws = self.scratch('_head_ws', L.dbn_head_tail_bwd_ws_floats())
-        G = self.grad_views
         hb, ht = 'segmentation_head.binarize.4', 'segmentation_head.thresh.4'
-        bn_sums = self.fbuf('head/bn4_sums', 4, 64)  # the kernel also reduces what the two BatchNorm backwards need
-        # reads both 64-channel ConvT outputs, the maps and their gradients; writes both 64-channel gradients
-        self._prof_hbm('head_tail_bwd_kernel + fold_head_grads_kernel + fold_partials_d_kernel', 4.0 * dz1b.element_size() * dz1b.numel() + 4.0 * (out.numel() + dpreds.numel()))
-        check(L.dbn_head_tail_bwd_t(self.at, B['binarize/y1'].data_ptr(), B['thresh/y1'].data_ptr(), b6.weight.data_ptr(),
-                                  t6.weight.data_ptr(), out.data_ptr(), dpreds.data_ptr(), B[hb + '/scale'].data_ptr(),
-                                  B[hb + '/shift'].data_ptr(), B[ht + '/scale'].data_ptr(), B[ht + '/shift'].data_ptr(),
-                                  B[hb + '/mean'].data_ptr(), B[hb + '/rstd'].data_ptr(), B[ht + '/mean'].data_ptr(),
-                                  B[ht + '/rstd'].data_ptr(), bn_sums.data_ptr(), dz1b.data_ptr(), dz1t.data_ptr(),
-                                  G['segmentation_head.binarize.6.weight'].data_ptr(),
-                                  G['segmentation_head.binarize.6.bias'].data_ptr(),
-                                  G['segmentation_head.thresh.6.weight'].data_ptr(),
-                                  G['segmentation_head.thresh.6.bias'].data_ptr(), N, Hh, Wh, 3, float(head.k),
-                                  self.grad_scale, ws.data_ptr(), st), 'head_tail_bwd')
-        if self.prof:
-            self.prof.end()
+        # train-mode BatchNorm coefficients of both branches at hand: the head tail and the two `.4` BatchNorm backwards in one call
+        fused = self.head_bwd_fused and self.at in self.head_bwd_fused_ats and all(
+            h + k in B for h in (hb, ht) for k in ('/scale', '/shift', '/mean', '/rstd'))
+        head_dy1 = self._head_tail_bn_bwd(out, dpreds, N, Hh, Wh) if fused else None
+        if not fused:
+            head_dy1 = self._head_tail_bwd(out, dpreds, N, Hh, Wh)
         f, f_act = B.get('fpn/z'), None
         if f is None:  # apply-on-load (see forward)
             f, f_act = B['fpn/y'], (B['segmentation_body.conv.1/scale'], B['segmentation_body.conv.1/shift'])
         df = self.buf('fpn/dz', *f.shape)
         fpn = m.segmentation_body
         pre = 'segmentation_body.'
-        for i, (br, dz1) in enumerate((('binarize', dz1b), ('thresh', dz1t))):
+        for i, br in enumerate(('binarize', 'thresh')):
             # (running the two branches' backward on two streams was tried: the join before the FPN backward makes the main
             # stream wait for every queued weight gradient and costs more than it gains)
             seq = getattr(head, br)
             hp = 'segmentation_head.%s.' % br
-            dy1 = self.bn_backward(hp + '4', B[br + '/y1'], 'self', dz1, br + '/dy1', sums=bn_sums[2 * i:2 * i + 2],
-                                   conv_bias=hp + '3.bias' if seq[3].bias is not None else None)
+            if fused:
+                self._flush_wgrads()  # (where the `.4` BatchNorm backward of the unfused sequence starts the queued weight gradients)
+                dy1 = head_dy1[i]
+            else:
+                dz1, bn_sums = head_dy1[i], head_dy1[2]
+                dy1 = self.bn_backward(hp + '4', B[br + '/y1'], 'self', dz1, br + '/dy1', sums=bn_sums[2 * i:2 * i + 2],
+                                       conv_bias=hp + '3.bias' if seq[3].bias is not None else None)
             dz0 = self.buf(br + '/dz0', *B[br + '/z0'].shape)
             self.convT_bwd(hp + '3', dy1, B[br + '/z0'], seq[3], dz0, consumer=(hp + '1', B[br + '/y0'], None))
             dy0 = self.bn_backward(hp + '1', B[br + '/y0'], 'self', dz0, br + '/dy0',

@@ -827,6 +827,19 @@ int dbn_head_tail_bwd_t(int at, const void* xb, const void* xt, const float* wb,
                         const float* bn_shift_t, const float* bn_mean_b, const float* bn_rstd_b, const float* bn_mean_t,
                         const float* bn_rstd_t, float* bn_sums, void* dxb, void* dxt, float* dw_b, float* dbias_b, float* dw_t,
                         float* dbias_t, int N, int Hq, int Wq, int channels, float kstep, float grad_scale, float* ws, void* stream);
+/* dbn_head_tail_bwd_t (with bn_sums) and the dbn_bn_backward_t of both branches' BatchNorm in front of the last ConvT (sums given, ReLU
+ * mask recomputed from scale / shift, dbias_conv) as ONE call with the same results bit for bit: the two [N Hq Wq][64] gradients between
+ * them are formed again inside the BatchNorm apply pass and never stored.  yb / yt: the BatchNorm inputs, dyb / dyt their gradients
+ * (storage type `at`); dbias_conv_b / _t optional [64] (both or neither); ws: dbn_head_tail_bn_bwd_ws_floats() floats.
+ * phases: 3 = the whole; 1 (sums pass, folds, finalize) then 2 (apply pass, bias fold) with the same arguments and workspace = the same
+ * launches as two calls, for a caller that times the two passes separately. */
+int dbn_head_tail_bn_bwd_ws_floats(void);
+int dbn_head_tail_bn_bwd_t(int at, int phases, const void* yb, const void* yt, const float* wb, const float* wt, const float* preds, const float* dpreds,
+                           const float* bn_scale_b, const float* bn_shift_b, const float* bn_scale_t, const float* bn_shift_t,
+                           const float* bn_mean_b, const float* bn_rstd_b, const float* bn_mean_t, const float* bn_rstd_t,
+                           const float* bn_gamma_b, const float* bn_gamma_t, void* dyb, void* dyt, float* dgamma_b, float* dbeta_b,
+                           float* dgamma_t, float* dbeta_t, float* dbias_conv_b, float* dbias_conv_t, float* dw_b, float* dbias_b, float* dw_t,
+                           float* dbias_t, int N, int Hq, int Wq, int channels, float kstep, float grad_scale, float* ws, void* stream);
 
 /* ---- JPEG decode for the device pipeline (csrc/jpeg.hip): in the place of cv2.imread(path)[:, :, ::-1] (data_loaders.py:78, utils.py:179).
  * The entropy stage runs on the host, the rest (dequantise, libjpeg's slow-integer IDCT, fancy chroma upsampling, YCbCr -> RGB) on the device.
