@@ -46,6 +46,7 @@ SIGNATURES = {
     'dbn_perspective_maps': 'piiipp',
     'dbn_warp_perspective_u8': 'plppiiiplp',
     'dbn_draw_strokes': 'pplpipliiiip',
+    'dbn_draw_glyphs': 'pplpiplpipliiiiip',
     'dbn_render_minmax': 'ppilplliifpp',
     'dbn_render_paint': 'ppppilplliifppfp',
     'dbn_minmax_scale_u8': 'piiippp',

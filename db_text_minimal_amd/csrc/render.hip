@@ -1,6 +1,8 @@
 // Showing a detection result on the device: the last step of the reference's inference path (utils.py:202-283, test.py,
 // test_ocr.py, test_webcam.py), on packed ragged uint8 HWC images (the layout of image_collate):
 //   draw_strokes     utils.draw_bbox: cv2.polylines(img.copy(), [pts], True, color, thickness) of every box / polygon
+//   draw_glyphs      the cv2.putText step of test_ocr.py / test_webcam.py: labels as filled DejaVu Sans outlines (this
+//                    project's definition, see "labels" below)
 //   render_minmax    the minimum and maximum, per image, of the probability map resized to that image (what
 //                    plt.imshow(tmp_pred) autoscales to); the resized values are never stored
 //   render_paint     cv2.resize(prob, (W, H)) INTER_LINEAR in float -> matplotlib Normalize -> Colormap byte table ->
@@ -115,6 +117,94 @@ __global__ void __launch_bounds__(RD_THREADS) draw_strokes_kernel(unsigned char*
             const int px = steep ? v : u, py = steep ? u : v;
             const bool hit = t == 1 ? on_line64(px, py, xa, ya, xb, yb) : stroke_hit(px, py, xa, ya, xb, yb, t);
             if (hit) {
+                unsigned char* o = img + ((long)py * W + px) * 3;
+                o[0] = (unsigned char)c0;
+                o[1] = (unsigned char)c1;
+                o[2] = (unsigned char)c2;
+            }
+        }
+    }
+}
+
+// ---- labels: filled glyph outlines ---------------------------------------------------------------------------------------
+// The last step of test_ocr.py:197-210 / test_webcam.py:274-284 (cv2.putText of every recognised string).  THIS PROJECT'S
+// DEFINITION, not cv2's Hershey strokes: the outlines of DejaVu Sans (fonts/dejavu_sans.txt: integer font units, 2048 per
+// em, quadratics already flattened into chords), filled by the non-zero winding rule at pixel centres, on or off, in
+// exact integers.  PARITY UNPINNED against cv2.putText by construction.
+//
+// The lattice is 1 / L pixel, L = 64 * 2048 = 2^17; size64 is the em size in 1/64 pixel.  Relative to the pen of a glyph
+// instance (org = the left end of the baseline, pen = the advances before it in font units) a vertex v sits at
+// v * size64 and the centre of pixel (px, py) at
+//   Px = ((64 px + 32) - 64 org.x) * 2048 - pen * size64,   Py = (64 org.y - (64 py + 32)) * 2048     (font y points up)
+// and an edge a -> b counts +1 if ay <= Py < by and cr > 0, -1 if by <= Py < ay and cr < 0, with
+// cr = (bx - ax)(Py - ay) - (by - ay)(Px - ax); the pixel is painted iff the sum over the glyph's edges is not 0.
+//
+// 64 bits suffice.  Only pixels whose centre lies inside the glyph's bounding box (xmin, ymin, xmax, ymax of the index,
+// scaled) are evaluated, and an instance is skipped unless X = (xmax - xmin) size64 < 2^35 and Y = (ymax - ymin) size64 <
+// 2^27.  Edge ends and the centre then lie in one X by Y rectangle, so both products of cr are below 2^62 and cr below
+// 2^63.  The font's own glyphs stay far inside: |v| <= 2048 + 106 font units and size64 <= rint(512 * 64 * 2048 / 1493) =
+// 44 949 < 2^15.5 give coordinates below 2^29 and products below 2^58.  The background rectangle of a label (at most 256
+// advances of at most 2048 units wide, ascender - descender = 2384 units high, plus its margin) reaches X < 2^34.5, Y <
+// 2^26.8.  Before the box is known, L org (|org| <= 2^20), pen size64 (pen < 2^20) and L px (px < 2^16) are below 2^37.
+//
+// One workgroup owns one glyph instance; its waves stage the glyph's scaled edges in LDS once (at most GL_EDGES; a glyph
+// with more is skipped) and walk the clipped box in bands of GL_BAND rows, blockIdx.y striding the bands.  A pixel reads
+// every edge (all lanes read the same LDS address: a broadcast) and skips those whose y range misses it.  Only painted
+// pixels are stored, as three bytes.  One colour per launch: overlapping glyphs store the same bytes, as the strokes do.
+constexpr int GL_EDGES = 512, GL_BAND = 16;
+constexpr int GL_GLYPH = 6;  // int per glyph of the index: first edge, edges, xmin, ymin, xmax, ymax (font units)
+constexpr int GL_REC = 5;    // int per instance: image, glyph, pen (font units), org x, org y
+constexpr int GL_EDGE = 4;   // int per edge: ax, ay, bx, by (font units)
+constexpr long long GL_L = 64LL * 2048;
+
+__global__ void __launch_bounds__(RD_THREADS) draw_glyphs_kernel(unsigned char* __restrict__ dst, long bytes, const long long* __restrict__ desc,
+                                                                  int N, const int* __restrict__ edges, long E, const int* __restrict__ glyphs,
+                                                                  int G, const int* __restrict__ recs, int size64, int c0, int c1, int c2) {
+    __shared__ long long s_e[GL_EDGES * GL_EDGE];
+    const int* rc = recs + (long)blockIdx.x * GL_REC;
+    const int n = rc[0], g = rc[1], pen = rc[2], ox = rc[3], oy = rc[4];
+    if (n < 0 || n >= N || g < 0 || g >= G || pen < 0 || pen > ST_VMAX || ox < -ST_VMAX || ox > ST_VMAX || oy < -ST_VMAX || oy > ST_VMAX) return;
+    const long long off = desc[(long)n * RD_IDESC], H = desc[(long)n * RD_IDESC + 1], W = desc[(long)n * RD_IDESC + 2];
+    if (H < 1 || W < 1 || H > 65535 || W > 65535 || off < 0 || off + H * W * 3 > bytes) return;
+    const int* gi = glyphs + (long)g * GL_GLYPH;
+    const long e0 = gi[0];
+    const int ne = gi[1];
+    const long long s = size64;
+    const long long gx0 = gi[2], gy0 = gi[3], gx1 = gi[4], gy1 = gi[5];
+    if (e0 < 0 || ne < 1 || ne > GL_EDGES || e0 + ne > E || gx1 < gx0 || gy1 < gy0) return;
+    if (gx0 < -ST_VMAX || gx1 > ST_VMAX || gy0 < -ST_VMAX || gy1 > ST_VMAX || (gx1 - gx0) * s >= (1LL << 35) || (gy1 - gy0) * s >= (1LL << 27)) return;
+    // the pixels whose centre lies in the box: gx0 s <= Px <= gx1 s, gy0 s <= Py <= gy1 s
+    const long long bx = GL_L * ox + pen * s - GL_L / 2, by = GL_L * oy - GL_L / 2;  // Px = L px - bx, Py = by - L py
+    long long x_lo = floor_div(gx0 * s + bx + GL_L - 1, GL_L), x_hi = floor_div(gx1 * s + bx, GL_L);
+    long long y_lo = floor_div(by - gy1 * s + GL_L - 1, GL_L), y_hi = floor_div(by - gy0 * s, GL_L);
+    x_lo = x_lo < 0 ? 0 : x_lo;
+    y_lo = y_lo < 0 ? 0 : y_lo;
+    x_hi = x_hi > W - 1 ? W - 1 : x_hi;
+    y_hi = y_hi > H - 1 ? H - 1 : y_hi;
+    if (x_lo > x_hi || y_lo > y_hi) return;
+    const int cols = (int)(x_hi - x_lo + 1), rows = (int)(y_hi - y_lo + 1);
+    if ((long)blockIdx.y * GL_BAND >= rows) return;
+    for (int i = threadIdx.x; i < ne * GL_EDGE; i += RD_THREADS) s_e[i] = (long long)edges[e0 * GL_EDGE + i] * s;
+    __syncthreads();
+    unsigned char* img = dst + off;
+    for (int r0 = blockIdx.y * GL_BAND; r0 < rows; r0 += gridDim.y * GL_BAND) {
+        const int nr = rows - r0 < GL_BAND ? rows - r0 : GL_BAND;
+        const unsigned cnt = (unsigned)nr * (unsigned)cols;  // <= 16 * 65535
+        for (unsigned i = threadIdx.x; i < cnt; i += RD_THREADS) {
+            const unsigned r = i / (unsigned)cols;
+            const long long px = x_lo + (i - r * (unsigned)cols), py = y_lo + r0 + r;
+            const long long Px = GL_L * px - bx, Py = by - GL_L * py;
+            int wn = 0;
+            for (int e = 0; e < ne; ++e) {
+                const long long ay = s_e[e * GL_EDGE + 1], byy = s_e[e * GL_EDGE + 3];
+                const bool up = ay <= Py && Py < byy, down = byy <= Py && Py < ay;
+                if (up || down) {
+                    const long long ax = s_e[e * GL_EDGE], bxx = s_e[e * GL_EDGE + 2];
+                    const long long cr = (bxx - ax) * (Py - ay) - (byy - ay) * (Px - ax);
+                    wn += (up && cr > 0) ? 1 : ((down && cr < 0) ? -1 : 0);
+                }
+            }
+            if (wn != 0) {
                 unsigned char* o = img + ((long)py * W + px) * 3;
                 o[0] = (unsigned char)c0;
                 o[1] = (unsigned char)c1;
@@ -396,6 +486,21 @@ int dbn_draw_strokes(const unsigned char* src, unsigned char* dst, long bytes, c
     if (E > 0)
         hipLaunchKernelGGL(draw_strokes_kernel, dim3((unsigned)blocks), dim3(RD_THREADS), 0, (hipStream_t)stream, dst, bytes, desc, N, edges, E,
                            thickness, c0, c1, c2);
+    return dbn_status();
+}
+
+int dbn_draw_glyphs(const unsigned char* src, unsigned char* dst, long bytes, const long long* desc, int N, const int* edges, long E,
+                    const int* glyphs, int G, const int* recs, long R, int size64, int rows, int c0, int c1, int c2, void* stream) {
+    DBN_REQUIRE(src && dst && desc && bytes > 0 && N > 0 && R >= 0 && R <= 2147483647L && (R == 0 || (edges && glyphs && recs && E > 0 && G > 0)));
+    DBN_REQUIRE(size64 >= 1 && size64 <= 65536 && rows >= 1 && rows <= 65535);
+    DBN_REQUIRE(c0 >= 0 && c0 <= 255 && c1 >= 0 && c1 <= 255 && c2 >= 0 && c2 <= 255);
+    if (src != dst) {
+        const hipError_t e = hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        if (e != hipSuccess) return 1000 + (int)e;
+    }
+    if (R > 0)
+        hipLaunchKernelGGL(draw_glyphs_kernel, dim3((unsigned)R, (unsigned)((rows + GL_BAND - 1) / GL_BAND)), dim3(RD_THREADS), 0, (hipStream_t)stream,
+                           dst, bytes, desc, N, edges, E, glyphs, G, recs, size64, c0, c1, c2);
     return dbn_status();
 }
 

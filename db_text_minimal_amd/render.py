@@ -7,6 +7,8 @@ over it at alpha = 0.6 (utils.visualize_polygon :252-283, utils.visualize_heatma
   overlay_heatmap(images, prob, valid_hw, cmap, alpha, ...)    the resized, coloured, blended map: one launch, plus one
                                                               reduction launch when the colour limits are autoscaled
   render_detections(images, prob, shapes, ...)                both, in the reference's order (outlines, then the map)
+  draw_labels(images, labels_per_image, color, height, ...)   the cv2.putText step of test_ocr.py:197-210: one launch
+  draw_words / draw_scores / draw_dots / text_size            recognised strings with anchor dots; scores; the label's box
   minmax_scale_u8(x)                                          utils.minmax_scaler_img (:110-113) of fp32 [N, 3, H, W]
   image_views(packed, shapes)                                 per-image [H, W, 3] views of a packed result
 
@@ -27,7 +29,12 @@ subtraction and the division in double, each stored as float32); index = Colorma
 figure resolution (the reference saves a 200-dpi figure), which is not reproducible pixel for pixel: UNPINNED.  The map
 must be finite.  DESIGN section 21.
 
-  python -m db_text_minimal_amd.render --image X --model_path M [--is_output_polygon] [--heatmap] [--out Y]
+Labels.  LABEL TEXT IS THIS PROJECT'S DEFINITION, not cv2.putText's Hershey strokes (neither cv2 nor the Hershey table is
+available here): the outlines of DejaVu Sans (fonts/dejavu_sans.txt, generated from the font matplotlib bundles by
+fonts/make_glyphs.py), filled by the non-zero winding rule at pixel centres in exact integers; a pixel is on or off.
+PARITY UNPINNED against cv2 by construction; pinned against matplotlib's own containment test on the CPU.  DESIGN section 29.
+
+  python -m db_text_minimal_amd.render --image X --model_path M [--is_output_polygon] [--heatmap] [--scores] [--out Y]
 """
 import os
 
@@ -42,8 +49,12 @@ CMAPS = ('inferno', 'jet')
 _VERT_MAX = 2 ** 20  # |vertex coordinate| of a shape (csrc/render.hip)
 _INT_MAX = 2 ** 31 - 1
 _EDGE, _IDESC, _PDESC, _COEF = 5, 3, 5, 4
+_GEDGE, _GLYPH, _REC = 4, 6, 5  # int32 per edge, glyph and glyph instance of dbn_draw_glyphs
+_FIRST, _LAST, _LABEL_MAX, _GLYPH_EDGES = 32, 126, 256, 512
+_LATTICE = 64 * 2048  # label coordinates are 1 / _LATTICE pixel
 LAUNCH_LOG = []  # the C entry points called, in order (tests clear it and read it back)
 _tables = {}
+_font, _font_dev = {}, {}
 
 
 def colormap_table(name):
@@ -274,16 +285,323 @@ def overlay_heatmap(images, prob, valid_hw=None, cmap='inferno', alpha=0.6, vmin
     return out
 
 
+# ---- labels ----------------------------------------------------------------------------------------------------------
+def glyph_table():
+    """the shipped font (fonts/dejavu_sans.txt, written by fonts/make_glyphs.py): a dict of `units_per_EM`, `ascender`,
+    `descender`, `cap_height`, `first` (code point of glyph 0), `advance` (int64 [G]), `contours` (per glyph a list of
+    int64 [P, 2] closed polylines in font units), and what the kernel takes: `edges` (int32 [E, 4] of ax, ay, bx, by;
+    every contour closed, horizontal edges left out: the winding rule never counts them) and `index` (int32 [G, 6] of
+    first edge, edges, xmin, ymin, xmax, ymax)"""
+    if _font:
+        return _font
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'fonts', 'dejavu_sans.txt')
+    head, adv, contours, want = {}, [], [], 0
+    for line in open(path):
+        f = line.split()
+        if not f:
+            continue
+        if f[0] == '#':
+            if len(f) == 3 and f[1] in ('units_per_EM', 'ascender', 'descender', 'cap_height'):
+                head[f[1]] = int(f[2])
+        elif f[0] == 'glyph':
+            if want or int(f[1]) != _FIRST + len(adv):
+                raise ValueError('%s: glyph %s out of order' % (path, f[1]))
+            adv.append(int(f[2]))
+            contours.append([])
+            want = int(f[3])
+        else:
+            v = np.array([int(t) for t in f], np.int64)
+            if not want or len(v) % 2 or len(v) < 6:
+                raise ValueError('%s: a stray contour line' % path)
+            contours[-1].append(v.reshape(-1, 2))
+            want -= 1
+    if len(adv) != _LAST - _FIRST + 1 or want or len(head) != 4:
+        raise ValueError('%s is not the table of code points %d .. %d' % (path, _FIRST, _LAST))
+    edges, index = [], np.zeros((len(adv), _GLYPH), np.int32)
+    for g, cs in enumerate(contours):
+        first = sum(len(e) for e in edges)
+        for c in cs:
+            e = np.concatenate([c, np.roll(c, -1, 0)], 1)
+            edges.append(e[e[:, 1] != e[:, 3]])
+        if cs:
+            p = np.concatenate(cs)
+            index[g] = first, sum(len(e) for e in edges) - first, p[:, 0].min(), p[:, 1].min(), p[:, 0].max(), p[:, 1].max()
+    if index[:, 1].max() > _GLYPH_EDGES:
+        raise ValueError('%s: a glyph of more than %d edges' % (path, _GLYPH_EDGES))
+    _font.update(head, first=_FIRST, advance=np.array(adv, np.int64), contours=contours, edges=np.concatenate(edges).astype(np.int32), index=index)
+    return _font
+
+
+def _font_on(dev):
+    if dev not in _font_dev:
+        f = glyph_table()
+        _font_dev[dev] = (_to_device(f['edges'], dev), _to_device(f['index'], dev))
+    return _font_dev[dev]
+
+
+def _size64(height):
+    """the em size in 1/64 pixel of a cap height in pixels: rint(height * 64 * units_per_EM / cap_height)"""
+    try:
+        h = float(height)
+    except (TypeError, ValueError):
+        raise ValueError('height must be a number in 4 .. 512, got %r' % (height, ))
+    if isinstance(height, bool) or not 4.0 <= h <= 512.0:
+        raise ValueError('height (the cap height in pixels) must lie in 4 .. 512, got %r' % (height, ))
+    f = glyph_table()
+    return int(np.rint(h * 64 * f['units_per_EM'] / f['cap_height']))
+
+
+def _glyphs_of(text):
+    if not isinstance(text, str):
+        raise ValueError('a label\'s text must be a str, got %r' % (text, ))
+    if len(text) > _LABEL_MAX:
+        raise ValueError('a label holds at most %d characters, got %d' % (_LABEL_MAX, len(text)))
+    return [(ord(ch) if _FIRST <= ord(ch) <= _LAST else ord('?')) - _FIRST for ch in text]
+
+
+def _ceil_px(v, size64):
+    return -((-int(v) * size64) // _LATTICE)
+
+
+def text_size(text, height=16):
+    """(width, ascent, descent) of a label in whole pixels, rounded up, as cv2.getTextSize gives its box: the advances of
+    the characters, the font's ascender above the baseline and its descender below it, at cap height `height`.  Host only."""
+    s, f = _size64(height), glyph_table()
+    return _ceil_px(f['advance'][_glyphs_of(text)].sum(), s), _ceil_px(f['ascender'], s), _ceil_px(-f['descender'], s)
+
+
+def _labels_of(labels_per_image, N):
+    ls = labels_per_image
+    if N == 1 and isinstance(ls, (list, tuple)) and len(ls) > 0 and isinstance(ls[0], (list, tuple)) and len(ls[0]) == 2 and isinstance(ls[0][0], str):
+        ls = [ls]
+    if not isinstance(ls, (list, tuple)) or len(ls) != N:
+        raise ValueError('labels for %s images, but %d images' % (len(ls) if isinstance(ls, (list, tuple)) else '?', N))
+    out = []
+    for n, entry in enumerate(ls):
+        rows = []
+        for lab in entry:
+            try:
+                text, (x, y) = lab
+                ok = int(x) == x and int(y) == y and abs(int(x)) <= _VERT_MAX and abs(int(y)) <= _VERT_MAX
+            except (TypeError, ValueError):
+                raise ValueError('a label of image %d must be (text, (x, y)), got %r' % (n, lab))
+            if not ok:
+                raise ValueError('the origin of a label of image %d must be integers within +-%d, got %r' % (n, _VERT_MAX, (x, y)))
+            if not isinstance(text, str) or len(text) > _LABEL_MAX:
+                _glyphs_of(text)  # raises
+            rows.append((text, int(x), int(y)))
+        out.append(rows)
+    return out
+
+
+def label_records(labels_per_image, N):
+    """-> int32 [R, 5] of (image, glyph, pen, x, y): one row per character that has an outline, the pen of character k
+    the sum of the advances before it (font units)"""
+    f = glyph_table()
+    flat = [(n, ) + lab for n, labs in enumerate(_labels_of(labels_per_image, N)) for lab in labs if lab[0]]
+    if not flat:
+        return np.zeros((0, _REC), np.int32)
+    lens = np.array([len(lab[1]) for lab in flat], np.int64)
+    codes = np.frombuffer(''.join(lab[1] for lab in flat).encode('utf-32-le', 'surrogatepass'), np.uint32).astype(np.int64)
+    g = np.where((codes >= _FIRST) & (codes <= _LAST), codes, ord('?')) - _FIRST
+    adv = f['advance'][g]
+    before = np.cumsum(adv) - adv  # the advances before each character in the whole run; minus those before its label's first
+    pen = before - np.repeat(before[np.cumsum(lens) - lens], lens)
+    nxy = np.repeat(np.array([(lab[0], lab[2], lab[3]) for lab in flat], np.int64), lens, 0)
+    recs = np.stack([nxy[:, 0], g, pen, nxy[:, 1], nxy[:, 2]], 1)
+    return recs[f['index'][g, 1] > 0].astype(np.int32)
+
+
+def label_backgrounds(labels_per_image, N, size64):
+    """the rectangles behind the labels, as a font of their own: (edges int32 [2 B, 4], index int32 [B, 6], records
+    int32 [B, 5]), one four-point contour per label (its two horizontal edges left out) from -m to the label's advance
+    + m and from descender - m to ascender + m, m = a 2-pixel margin rounded up to whole font units at this size"""
+    f = glyph_table()
+    m = -((-2 * _LATTICE) // size64)
+    y0, y1 = f['descender'] - m, f['ascender'] + m
+    edges, index, recs = [], [], []
+    for n, labs in enumerate(_labels_of(labels_per_image, N)):
+        for text, x, y in labs:
+            x0, x1 = -m, int(f['advance'][_glyphs_of(text)].sum()) + m
+            index.append((len(edges), 2, x0, y0, x1, y1))
+            edges += [(x1, y0, x1, y1), (x0, y1, x0, y0)]  # counter-clockwise with y up: right side up, left side down
+            recs.append((n, len(recs), 0, x, y))
+    return np.array(edges, np.int32).reshape(-1, _GEDGE), np.array(index, np.int32).reshape(-1, _GLYPH), np.array(recs, np.int32).reshape(-1, _REC)
+
+
+def _rows_bound(index, size64):
+    """an upper bound of the pixel rows of any glyph's box at this size"""
+    ext = int((index[:, 5].astype(np.int64) - index[:, 3]).max()) if len(index) else 0
+    return min(ext * size64 // _LATTICE + 2, 65535)
+
+
+def _out_buffer(packed, shapes, out, device):
+    """(src, out, device) of a paint-over: `out` holds the picture already and is painted in place, or the images are copied"""
+    if out is not None:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous()
+                and out.numel() == packed.numel() and (device is None or out.device == torch.device(device))):
+            raise ValueError('out must be a packed uint8 device tensor of %d bytes%s' % (packed.numel(), '' if device is None else ' on %s' % (device, )))
+        return out, out, out.device
+    dev = _device(packed, device)
+    src = _packed(packed, shapes, dev)
+    return src, torch.empty_like(src), dev
+
+
+def _image_desc(shapes, dev):
+    desc = np.stack([_offsets([h * w * 3 for h, w in shapes])[:-1], [h for h, _ in shapes], [w for _, w in shapes]], 1).astype(np.int64)
+    return _to_device(desc, dev)
+
+
+def draw_labels(images, labels_per_image, color=(255, 0, 0), height=16, background=None, out=None, device=None):
+    """The cv2.putText step of test_ocr.py:197-210 / test_webcam.py:274-284 for a batch: every label written onto its image.
+
+    labels_per_image: per image a list of (text, (x, y)); for a single image also that list itself.  (x, y), integers
+    within +-2^20, is the left end of the baseline, as cv2's org; text may run off the image or lie outside it.  height: the
+    cap height in pixels (a float in 4 .. 512; 16 is about what FONT_HERSHEY_SIMPLEX gives at scale 0.75).  Characters
+    are laid left to right by their advances, no kerning, no line breaks; one outside ASCII 32 .. 126 is drawn as '?'; at
+    most 256 per label; empty strings and empty lists are legal.  background=(r, g, b) first fills each label's
+    rectangle (its advance by ascender to descender, plus a 2-pixel margin) in a launch of its own.
+
+    LABEL TEXT IS THIS PROJECT'S DEFINITION, not cv2's Hershey strokes: the outlines of DejaVu Sans (fonts/dejavu_sans.txt),
+    filled by the non-zero winding rule at pixel centres in exact integers: a pixel is on or off, nothing is
+    anti-aliased (neither is cv2's LINE_8 text).  PARITY UNPINNED against cv2.putText by construction.  DESIGN section 29.
+
+    Returns the packed uint8 device copy with the labels; out: a packed uint8 device buffer that already holds the picture
+    (e.g. the result of draw_outlines), painted in place and returned, `images` then only gives the shapes.  One launch
+    (dbn_draw_glyphs), two with a background, on the current stream."""
+    packed, shapes = _images(images)
+    c = _color(color)
+    bg = _color(background) if background is not None else None
+    s = _size64(height)
+    N = len(shapes)
+    recs = label_records(labels_per_image, N)
+    src, out, dev = _out_buffer(packed, shapes, out, device)
+    if src.numel() == 0:
+        return out
+    d = _image_desc(shapes, dev)
+    if bg is not None:
+        e, g, r = label_backgrounds(labels_per_image, N, s)
+        te, tg, tr = (_to_device(a, dev) if len(a) else None for a in (e, g, r))
+        _call('dbn_draw_glyphs', src.data_ptr(), out.data_ptr(), src.numel(), d.data_ptr(), N, te.data_ptr() if len(r) else None, len(e),
+              tg.data_ptr() if len(r) else None, len(g), tr.data_ptr() if len(r) else None, len(r), s, _rows_bound(g, s), bg[0], bg[1], bg[2],
+              _stream(dev))
+        src = out
+    fe, fg = _font_on(dev)
+    tr = _to_device(recs, dev) if len(recs) else None
+    _call('dbn_draw_glyphs', src.data_ptr(), out.data_ptr(), src.numel(), d.data_ptr(), N, fe.data_ptr(), fe.shape[0], fg.data_ptr(), fg.shape[0],
+          tr.data_ptr() if tr is not None else None, len(recs), s, _rows_bound(glyph_table()['index'], s), c[0], c[1], c[2], _stream(dev))
+    return out
+
+
+def draw_dots(images, points_per_image, color=(0, 255, 0), out=None, device=None):
+    """The anchor dots of test_ocr.py:202-205, cv2.circle(img, (x, y), radius=0, thickness=int(H * 0.01)): per image of
+    height H a disc of diameter d = int(H * 0.01) about every (x, y) of points_per_image[n], none where d is 0.  A disc is
+    one zero-length edge through dbn_draw_strokes (d = 1: the pixel itself; d >= 2: 4 r^2 <= d^2, this project's stroke):
+    one launch per distinct d > 0, in ascending order.  out: as draw_labels."""
+    packed, shapes = _images(images)
+    c = _color(color)
+    if not isinstance(points_per_image, (list, tuple)) or len(points_per_image) != len(shapes):
+        raise ValueError('points for %s images, but %d images' % (len(points_per_image) if isinstance(points_per_image, (list, tuple)) else '?', len(shapes)))
+    by_d = {}
+    for n, pts in enumerate(points_per_image):
+        d = min(int(shapes[n][0] * 0.01), 255)
+        for x, y in pts:
+            if int(x) != x or int(y) != y or abs(int(x)) > _VERT_MAX or abs(int(y)) > _VERT_MAX:
+                raise ValueError('a point of image %d must be integers within +-%d, got %r' % (n, _VERT_MAX, (x, y)))
+            if d > 0:
+                by_d.setdefault(d, []).append((n, int(x), int(y), int(x), int(y)))
+    src, out, dev = _out_buffer(packed, shapes, out, device)
+    if src.numel() == 0:
+        return out
+    desc = _image_desc(shapes, dev)
+    if not by_d and src is not out:
+        out.copy_(src)
+    for d in sorted(by_d):
+        e = _to_device(np.array(by_d[d], np.int32), dev)
+        _call('dbn_draw_strokes', src.data_ptr(), out.data_ptr(), src.numel(), desc.data_ptr(), len(shapes), e.data_ptr(), len(by_d[d]), d, c[0], c[1],
+              c[2], _stream(dev))
+        src = out
+    return out
+
+
+def _words_of(words_per_image, N):
+    ws = words_per_image
+    if N == 1 and isinstance(ws, (list, tuple)) and len(ws) > 0 and isinstance(ws[0], dict):
+        ws = [ws]
+    if not isinstance(ws, (list, tuple)) or len(ws) != N:
+        raise ValueError('words for %s images, but %d images' % (len(ws) if isinstance(ws, (list, tuple)) else '?', N))
+    out = []
+    for n, words in enumerate(ws):
+        rows = []
+        for w in words:
+            box = None if not isinstance(w, dict) or w.get('box') is None else np.asarray(w['box'])
+            if box is None or box.ndim != 2 or box.shape[0] < 1 or box.shape[1] != 2 or box.dtype.kind not in 'iu':
+                raise ValueError('a word of image %d must be {\'box\': integer [P, 2], \'pred\': str, ...} as recognize_words gives it' % n)
+            rows.append((str(w['pred']), (int(box[0, 0]), int(box[0, 1]))))
+        out.append(rows)
+    return out
+
+
+def draw_words(images, words_per_image, color=(255, 0, 0), height=16, dots=True, dot_color=(0, 255, 0), background=None, out=None, device=None):
+    """test_ocr.py:201-207 for a batch: words_per_image is the output of recognize_words (per image a list of {'box', 'pred',
+    'score'}); each `pred` is written at box[0], the first corner of its box, and with `dots` the anchor disc is drawn
+    there first.  The same bytes and launches as draw_dots(images, anchors, dot_color) followed by
+    draw_labels(..., out=that result), which is how it runs (all dots, then all text: the reference goes word by word, so
+    there a later dot may cover earlier text).  Label text is this project's definition (draw_labels), not cv2's."""
+    packed, shapes = _images(images)
+    labels = _words_of(words_per_image, len(shapes))
+    if dots:
+        out = draw_dots((packed, shapes), [[p for _, p in labs] for labs in labels], dot_color, out=out, device=device)
+    return draw_labels((packed, shapes), labels, color, height, background, out=out, device=device)
+
+
+def score_labels(detections_per_image, N, fmt='%.2f'):
+    """per image the (text, (x, y)) labels draw_scores writes: fmt % score at the first vertex of every shape that
+    draw_outlines draws (coordinate sum > 0)"""
+    d = detections_per_image
+    if N == 1 and _is_pair(d):
+        d = [d]
+    if not isinstance(d, (list, tuple)) or len(d) != N:
+        raise ValueError('detections for %s images, but %d images' % (len(d) if isinstance(d, (list, tuple)) else '?', N))
+    out = []
+    for n, entry in enumerate(d):
+        if not _is_pair(entry) or len(entry[0]) != len(entry[1]):
+            raise ValueError('detections of image %d must be the (shapes, scores) pair of detect_boxes / detect_polygons' % n)
+        rows = []
+        for p, sc in zip(entry[0], entry[1]):
+            p = np.asarray(p).astype(np.int64).reshape(-1, 2)
+            if len(p) and p.sum() > 0:
+                rows.append((fmt % float(sc), (int(p[0, 0]), int(p[0, 1]))))
+        out.append(rows)
+    return out
+
+
+def draw_scores(images, detections_per_image, fmt='%.2f', color=(255, 0, 0), height=16, background=None, out=None, device=None):
+    """Every detection's score written at its first vertex, for the (boxes, scores) pairs of detect_boxes and the (polygons,
+    scores) pairs of detect_polygons alike: draw_labels(images, score_labels(detections, N, fmt), ...).  Needs no
+    recogniser.  Label text is this project's definition (draw_labels), not cv2's."""
+    packed, shapes = _images(images)
+    return draw_labels((packed, shapes), score_labels(detections_per_image, len(shapes), fmt), color, height, background, out=out, device=device)
+
+
 def render_detections(images, prob, shapes_per_image, valid_hw=None, color=(255, 0, 0), thickness=3, cmap='inferno', alpha=0.6, vmin=None,
-                      vmax=None, heatmap=True):
+                      vmax=None, heatmap=True, words=None, scores=False, height=16):
     """utils.visualize_polygon's picture for a batch, in the reference's order (utils.py:252-275): the outlines of every
     shape on a copy of the images, then the heat map over everything.  The same bytes as draw_outlines followed by
-    overlay_heatmap(out=...), which is how it runs.  heatmap=False stops after the outlines (test_ocr.py / test_webcam.py)."""
+    overlay_heatmap(out=...), which is how it runs.  heatmap=False stops after the outlines (test_ocr.py / test_webcam.py).
+    scores=True then writes every detection's score (draw_scores(images, shapes_per_image, out=...)) and words= (the
+    output of recognize_words) the recognised strings with their anchor dots (draw_words(images, words, out=...)), in
+    that order, in `color` at cap height `height`, after the map so that they stay readable.  Label text is this
+    project's definition (draw_labels), not cv2.putText's."""
     packed, shapes = _images(images)
     out = draw_outlines((packed, shapes), shapes_per_image, color, thickness, device=prob.device if isinstance(prob, torch.Tensor) else None)
-    if not heatmap:
-        return out
-    return overlay_heatmap((packed, shapes), prob, valid_hw, cmap, alpha, vmin, vmax, out=out)
+    if heatmap:
+        out = overlay_heatmap((packed, shapes), prob, valid_hw, cmap, alpha, vmin, vmax, out=out)
+    if scores:
+        out = draw_scores((packed, shapes), shapes_per_image, color=color, height=height, out=out)
+    if words is not None:
+        out = draw_words((packed, shapes), words, color, height, out=out)
+    return out
 
 
 def minmax_scale_u8(x):
@@ -349,6 +667,7 @@ def main(argv=None):
     ap.add_argument('--model_path', required=True)
     ap.add_argument('--is_output_polygon', action='store_true')
     ap.add_argument('--heatmap', action='store_true', help='lay the probability map over the outlines (test.py)')
+    ap.add_argument('--scores', action='store_true', help='write every detection\'s score at its first vertex (draw_scores)')
     ap.add_argument('--out', default=None, help='.npy, .jpg / .jpeg (written by encode_jpeg), or another suffix when PIL is installed')
     ap.add_argument('--thresh', type=float, default=0.25)
     ap.add_argument('--box_thresh', type=float, default=0.5)
@@ -368,7 +687,7 @@ def main(argv=None):
         preds = torch.stack([p.reshape(p.shape[0], p.shape[-2], p.shape[-1]) for p in preds], 1)
     detect = detect_polygons if args.is_output_polygon else detect_boxes
     res = detect(preds, args.thresh, args.box_thresh, unclip_ratio=args.unclip_ratio, dest_sizes=[tuple(img.shape[:2])])
-    out = render_detections(img, preds, res, alpha=args.alpha, heatmap=args.heatmap)
+    out = render_detections(img, preds, res, alpha=args.alpha, heatmap=args.heatmap, scores=args.scores)
     path = args.out or os.path.splitext(args.image)[0] + ('_poly' if args.is_output_polygon else '_rect') + '_result.npy'
     _write_image(path, image_views(out, [tuple(img.shape[:2])])[0])
     print(path)

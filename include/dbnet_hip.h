@@ -464,6 +464,20 @@ int dbn_warp_perspective_u8(const unsigned char* src, long src_bytes, const long
  * whose image, descriptor or vertices break this is skipped.  E may be 0. */
 int dbn_draw_strokes(const unsigned char* src, unsigned char* dst, long bytes, const long long* desc, int N, const int* edges, long E,
                      int thickness, int c0, int c1, int c2, void* stream);
+/* Labels: the cv2.putText step of test_ocr.py:197-210, as filled glyph outlines (THIS PROJECT'S DEFINITION: DejaVu Sans,
+ * non-zero winding at pixel centres in exact integers, on or off; PARITY UNPINNED against cv2's Hershey strokes, DESIGN.md
+ * 29).  dst = src (as dbn_draw_strokes; src may be dst), then for each of R instances recs[r][5] = {image, glyph, pen,
+ * org x, org y} every pixel (px, py) of the image whose centre has a non-zero winding number about the glyph's contours is
+ * set to (c0, c1, c2).  On the lattice of 1 / (64 * 2048) pixel a vertex v sits at v * size64 and the centre at
+ * (((64 px + 32) - 64 org x) * 2048 - pen * size64, (64 org y - (64 py + 32)) * 2048); edge a -> b counts +1 if
+ * ay <= Py < by and cr > 0, -1 if by <= Py < ay and cr < 0, cr = (bx - ax)(Py - ay) - (by - ay)(Px - ax).
+ * edges[E][4] = {ax, ay, bx, by} and glyphs[G][6] = {first edge, edges, xmin, ymin, xmax, ymax} in font units (the box
+ * holds every edge of the glyph; only pixels with their centre inside it are tested); desc as dbn_draw_strokes.
+ * 0 <= pen <= 2^20, |org| <= 2^20, at most 512 edges per glyph, (xmax - xmin) size64 < 2^35, (ymax - ymin) size64 < 2^27:
+ * an instance whose image, descriptor, glyph or numbers break this is skipped.  rows: an upper bound of the pixel rows
+ * of a glyph's box (sizes the grid; any value 1 .. 65535 gives the same bytes).  R may be 0.  No float arithmetic. */
+int dbn_draw_glyphs(const unsigned char* src, unsigned char* dst, long bytes, const long long* desc, int N, const int* edges, long E,
+                    const int* glyphs, int G, const int* recs, long R, int size64, int rows, int c0, int c1, int c2, void* stream);
 /* The heat map.  desc[n][5] int64 = {first pixel of image n in the packed run of n_px pixels, height, width, valid map
  * rows, valid map columns}; coef[n][4] fp64 = {scale_x, scale_y (1 / ((double)dst / src), as cv2.resize), vmin, vmax}.
  * Image n's map is prob + n * img_stride, rows row_stride floats apart, map_elems floats in all.  binary != 0: a tap
