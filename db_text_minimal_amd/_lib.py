@@ -12,9 +12,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DBN_LIB_PATH') or os.path.join(_HERE, 'libdbnet_hip.so')
 CSRC = os.path.join(_HERE, 'csrc')
 
-_P, _I, _L, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
+_P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
 
-# name -> argument kinds (p = device/host pointer, i = int, l = long, f = float); all return int
+# name -> argument kinds (p = device/host pointer, i = int, l = long, f = float, d = double); all return int
 SIGNATURES = {
     'dbn_pack_weights': 'piiiiiipp',
     'dbn_igemm_panel_floats': 'iiiiii',
@@ -117,12 +117,12 @@ SIGNATURES = {
     'dbn_head_tail_bwd_ws_floats': '',
     'dbn_head_tail_bwd': 'p' * 21 + 'iiii' + 'ff' + 'pp',
     'dbn_db_loss_ws_bytes': '',
-    'dbn_db_loss_fwd': 'pp' + 'iiii' + 'ffff' + 'pppp',
-    'dbn_db_loss_sum_fwd': 'pp' + 'iiii' + 'ffff' + 'pppp',
-    'dbn_db_loss_frac_fwd': 'pp' + 'iiii' + 'ffff' + 'i' + 'pppp',
+    'dbn_db_loss_fwd': 'pp' + 'iiii' + 'ffdf' + 'pppp',
+    'dbn_db_loss_sum_fwd': 'pp' + 'iiii' + 'ffdf' + 'pppp',
+    'dbn_db_loss_frac_fwd': 'pp' + 'iiii' + 'ffdf' + 'i' + 'pppp',
     'dbn_db_loss_bwd': 'pppp' + 'ff' + 'iiii' + 'pp',
     'dbn_db_loss_ohem_ws_bytes': 'iii',
-    'dbn_db_loss_ohem_fwd': 'pp' + 'iiii' + 'ffff' + 'pppp',
+    'dbn_db_loss_ohem_fwd': 'pp' + 'iiii' + 'ffdf' + 'pppp',
     'dbn_db_loss_ohem_bwd': 'ppppp' + 'ff' + 'iiii' + 'pp',
     'dbn_pixel_confusion': 'plppiiifpp',
     'dbn_adam_step': 'pppp' + 'l' + 'ffff' + 'i' + 'f' + 'p',
@@ -235,7 +235,7 @@ SIGNATURES.update({
     'dbn_head_tail_bn_bwd_t': 'ii' + 'p' * 28 + 'iiii' + 'ff' + 'pp',
 })
 LONG_RETURN = {'dbn_jpeg_coef_elems', 'dbn_jpeg_coef_elems_ex', 'dbn_jpeg_dhuff_ws_bytes', 'dbn_jpeg_encode_bound', 'dbn_greedy_decode_ws_bytes', 'dbn_det_eval_ws_bytes', 'dbn_detect_ws_bytes', 'dbn_detect_poly_ws_bytes', 'dbn_detect_poly_verts_cap', 'dbn_mfma_sustained_flops', 'dbn_conv_bn_final_group_doubles', 'dbn_maxpool_bn_backward_ws_floats', 'dbn_pw16_panel_bytes', 'dbn_stem16_panel_bytes', 'dbn_convt16_panel_bytes', 'dbn_winograd_panel_floats', 'dbn_winograd_wgrad_slab_floats', 'dbn_winograd_ws_floats', 'dbn_igemm_splitk_slab_floats', 'dbn_deform_col2im_ws_bytes', 'dbn_deform_col2im_gather_ws_bytes', 'dbn_igemm_bn_final_counters', 'dbn_igemm_bn_final_group_floats', 'dbn_igemm_panel_floats_t', 'dbn_wgrad_slab_floats_hw', 'dbn_wgrad_slab_floats', 'dbn_igemm_panel_floats', 'dbn_igemm_bf16s_panel_floats', 'dbn_db_loss_ohem_ws_bytes', 'dbn_conv_bn_ws_floats', 'dbn_pyramid_conv_ws_floats'}
-_KIND = {'p': _P, 'i': _I, 'l': _L, 'f': _F}
+_KIND = {'p': _P, 'i': _I, 'l': _L, 'f': _F, 'd': _D}
 
 
 class HipLibraryError(RuntimeError):

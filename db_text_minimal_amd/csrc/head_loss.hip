@@ -593,7 +593,8 @@ struct DbLossFinal {
     // arguments of the finalize step, run by the LAST workgroup of db_loss_fwd_kernel
     long px;
     int CH;
-    float alpha, beta, negative_ratio, eps;
+    float alpha, beta, eps;
+    double negative_ratio;  // a double through the whole ABI: int(n_pos * ratio) is taken in Python doubles (losses.py:26)
     int bce_sum;
     float* losses;
     float* coef;
@@ -609,7 +610,7 @@ struct DbLossFinal {
 __device__ __forceinline__ void db_loss_finish(const double (&s)[NSUM], const DbLossFinal& f) {
     // losses.py:25-28 — int() truncations
     const long n_pos = (long)(float)s[S_POS];
-    const long n_neg_expect = (long)((double)n_pos * (double)f.negative_ratio);
+    const long n_neg_expect = (long)((double)n_pos * f.negative_ratio);
     const long n_neg_cur = (long)(float)s[S_NEG];
     const long n_neg = n_neg_expect < n_neg_cur ? n_neg_expect : n_neg_cur;
     // reduction='mean' (default) / 'sum': F.binary_cross_entropy returns ONE scalar over all pixels (losses.py:30)
@@ -845,7 +846,7 @@ __device__ __forceinline__ bool ohem_prefix_match(unsigned bits, unsigned prefix
 }
 
 // k = n_neg from the folded sums; clears the select state.  One block.
-__global__ void ohem_prepare_kernel(const double* __restrict__ part, int nb, float negative_ratio, unsigned long long* __restrict__ st,
+__global__ void ohem_prepare_kernel(const double* __restrict__ part, int nb, double negative_ratio, unsigned long long* __restrict__ st,
                                     unsigned* __restrict__ hist) {
     __shared__ double sums[2];
     if (threadIdx.x < 64) {
@@ -860,7 +861,7 @@ __global__ void ohem_prepare_kernel(const double* __restrict__ part, int nb, flo
     __syncthreads();
     if (threadIdx.x == 0) {
         const long n_pos = (long)(float)sums[0];
-        const long n_exp = (long)((double)n_pos * (double)negative_ratio);
+        const long n_exp = (long)((double)n_pos * negative_ratio);
         const long n_cur = (long)(float)sums[1];
         st[0] = (unsigned long long)(n_exp < n_cur ? n_exp : n_cur);
         st[1] = 0;
@@ -1197,7 +1198,7 @@ static const long OHEM_OFF_POS = DB_LOSS_PART_BYTES + 64, OHEM_OFF_SEL = OHEM_OF
 long dbn_db_loss_ohem_ws_bytes(int N, int H, int W) { return OHEM_OFF_V + (long)N * H * W * 4; }
 
 static int db_loss_fwd_run(const float* preds, const float* gts, int N, int H, int W, int channels, float alpha, float beta,
-                           float negative_ratio, float eps, int per_pixel, float* losses, float* coef, void* ws, void* stream) {
+                           double negative_ratio, float eps, int per_pixel, float* losses, float* coef, void* ws, void* stream) {
     DBN_REQUIRE(preds && gts && losses && coef && ws && (channels == 2 || channels == 3));
     const long HW = (long)H * W;
     hipStream_t st = (hipStream_t)stream;
@@ -1207,7 +1208,7 @@ static int db_loss_fwd_run(const float* preds, const float* gts, int N, int H, i
     char* base = (char*)ws;
     // per_pixel: 0 'mean', 1 'none' (per-pixel OHEM), 2 'sum', 3 / 4 'mean' / 'sum' on non-binary maps (literal top-k of negative)
     const int frac = per_pixel >= 3, bce_sum = (per_pixel == 2 || per_pixel == 4) ? 1 : 0;
-    DbLossFinal fin = {(long)N * HW, channels, alpha, beta, negative_ratio, eps, bce_sum, losses, coef,
+    DbLossFinal fin = {(long)N * HW, channels, alpha, beta, eps, negative_ratio, bce_sum, losses, coef,
                        (unsigned*)(base + DB_LOSS_PART_BYTES)};
     if (hipMemsetAsync(fin.counter, 0, sizeof(unsigned), st) != hipSuccess) return dbn_status();
     if (vec)
@@ -1236,21 +1237,21 @@ static int db_loss_fwd_run(const float* preds, const float* gts, int N, int H, i
 
 // losses: [5] floats, coef: [8] floats (kept for the backward), ws: dbn_db_loss_ws_bytes()
 int dbn_db_loss_fwd(const float* preds, const float* gts, int N, int H, int W, int channels, float alpha, float beta,
-                    float negative_ratio, float eps, float* losses, float* coef, void* ws, void* stream) {
+                    double negative_ratio, float eps, float* losses, float* coef, void* ws, void* stream) {
     return db_loss_fwd_run(preds, gts, N, H, W, channels, alpha, beta, negative_ratio, eps, 0, losses, coef, ws, stream);
 }
 
 // DBLoss(reduction='sum'): like dbn_db_loss_fwd with the scalar BCE summed instead of averaged (losses.py:30 forwards the
 // reduction string to F.binary_cross_entropy); backward through dbn_db_loss_bwd with the coef written here.
 int dbn_db_loss_sum_fwd(const float* preds, const float* gts, int N, int H, int W, int channels, float alpha, float beta,
-                        float negative_ratio, float eps, float* losses, float* coef, void* ws, void* stream) {
+                        double negative_ratio, float eps, float* losses, float* coef, void* ws, void* stream) {
     return db_loss_fwd_run(preds, gts, N, H, W, channels, alpha, beta, negative_ratio, eps, 2, losses, coef, ws, stream);
 }
 
 // DBLoss(reduction='none'): true per-pixel OHEM (top n_neg negative losses, device radix select).
 // ws: dbn_db_loss_ohem_ws_bytes(N,H,W) bytes, must stay untouched until dbn_db_loss_ohem_bwd has run.
 int dbn_db_loss_ohem_fwd(const float* preds, const float* gts, int N, int H, int W, int channels, float alpha, float beta,
-                         float negative_ratio, float eps, float* losses, float* coef, void* ws, void* stream) {
+                         double negative_ratio, float eps, float* losses, float* coef, void* ws, void* stream) {
     return db_loss_fwd_run(preds, gts, N, H, W, channels, alpha, beta, negative_ratio, eps, 1, losses, coef, ws, stream);
 }
 
@@ -1259,7 +1260,7 @@ int dbn_db_loss_ohem_fwd(const float* preds, const float* gts, int N, int H, int
 // the per-pixel OHEM path.  (For binary maps it equals dbn_db_loss_fwd, which needs no select.)  `sum` != 0: reduction='sum'.
 // ws: dbn_db_loss_ohem_ws_bytes(N,H,W) bytes.  Backward: dbn_db_loss_bwd with the coef written here.
 int dbn_db_loss_frac_fwd(const float* preds, const float* gts, int N, int H, int W, int channels, float alpha, float beta,
-                         float negative_ratio, float eps, int sum, float* losses, float* coef, void* ws, void* stream) {
+                         double negative_ratio, float eps, int sum, float* losses, float* coef, void* ws, void* stream) {
     return db_loss_fwd_run(preds, gts, N, H, W, channels, alpha, beta, negative_ratio, eps, sum ? 4 : 3, losses, coef, ws, stream);
 }
 

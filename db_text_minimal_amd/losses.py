@@ -78,6 +78,7 @@ class _DBLossFunction(torch.autograd.Function):
         st = torch.cuda.current_stream(preds.device).cuda_stream
         losses = torch.empty(5, device=preds.device, dtype=torch.float32)
         coef = torch.zeros(8, device=preds.device, dtype=torch.float32)
+        # negative_ratio crosses the ABI as a double (a Python float is one): int(n_pos * ratio) truncates as in losses.py:26
         if per_pixel == 1:
             ws = torch.empty(L.dbn_db_loss_ohem_ws_bytes(N, H, W) // 4 + 1, device=preds.device, dtype=torch.float32)
             check(L.dbn_db_loss_ohem_fwd(preds.data_ptr(), gts.data_ptr(), N, H, W, C, alpha, beta, float(negative_ratio), eps,

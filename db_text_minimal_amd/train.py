@@ -243,6 +243,7 @@ class DBTrainer:
         eng = self.model.engine
         if eng.prof:  # reads the 3 maps and the 4 targets once
             eng.prof.begin('db_loss_fwd_kernel', 0.0, 4.0 * (preds.numel() + gts.numel()))
+        # (negative_ratio: a double through the ABI, like DBLoss.forward)
         if frac:
             check(L.dbn_db_loss_frac_fwd(preds.data_ptr(), gts.data_ptr(), N, H, W, C, c.alpha, c.beta, float(c.negative_ratio), c.eps,
                                          1 if reduction == 'sum' else 0, losses.data_ptr(), self._coef.data_ptr(), self._ws.data_ptr(), st),

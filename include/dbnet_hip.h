@@ -319,16 +319,18 @@ int dbn_winograd_wgrad_f32(int phases, const float* dy, const float* x, const fl
 /* ---- DBLoss (losses.py:18-40,48-66,75-82,105-139); preds [N,3|2,H,W], gts [4,N,H,W].
  * One launch: the workgroup that finishes last folds every workgroup's partial sums (fixed order) and writes losses[5] and
  * coef[8].  ws: dbn_db_loss_ws_bytes() bytes of scratch, no initialisation required (it ends with the arrival counter of that
- * hand-over, which the library clears on `stream` in front of every launch); not shared between calls that may run concurrently. */
+ * hand-over, which the library clears on `stream` in front of every launch); not shared between calls that may run concurrently.
+ * negative_ratio is a double in all four forward entry points: n_neg = min(int(n_pos * negative_ratio), ...) is taken in doubles like
+ * the reference's Python (losses.py:26); rounded to float first, 0.7, 2.3 or 3.3 truncate one lower at n_pos = 10, 20, ... */
 int dbn_db_loss_ws_bytes(void);
 int dbn_db_loss_fwd(const float* preds, const float* gts, int N, int H, int W, int channels, float alpha, float beta,
-                    float negative_ratio, float eps, float* losses, float* coef, void* ws, void* stream);
+                    double negative_ratio, float eps, float* losses, float* coef, void* ws, void* stream);
 int dbn_db_loss_bwd(const float* preds, const float* gts, const float* coef, const float* grad_losses, float alpha, float beta,
                     int N, int H, int W, int channels, float* dpreds, void* stream);
 /* DBLoss(reduction='sum'): losses.py:30 forwards the reduction string to F.binary_cross_entropy, so the scalar BCE of the
  * OHEM term is summed instead of averaged; everything else as dbn_db_loss_fwd (same ws; backward: dbn_db_loss_bwd). */
 int dbn_db_loss_sum_fwd(const float* preds, const float* gts, int N, int H, int W, int channels, float alpha, float beta,
-                        float negative_ratio, float eps, float* losses, float* coef, void* ws, void* stream);
+                        double negative_ratio, float eps, float* losses, float* coef, void* ws, void* stream);
 /* The two entry points above evaluate losses.py:33-39's `topk(loss * negative, n_neg).sum()` (loss a SCALAR in these reductions)
  * in closed form, bce * n_neg — exact for binary prob_gt / supervision_mask maps (what data_loaders.py:112-134 produces) and
  * only for those.  coef[7] receives the number of pixels whose gt or mask is neither 0 nor 1 (the host side refuses such maps,
@@ -336,14 +338,14 @@ int dbn_db_loss_sum_fwd(const float* preds, const float* gts, int N, int H, int 
  * bce * (sum(positive) + sum of the n_neg largest negative_i) / (n_pos + n_neg + eps), top-k sum by the device radix select of
  * the per-pixel path below.  sum != 0: reduction='sum'.  ws: dbn_db_loss_ohem_ws_bytes(N,H,W) bytes; backward: dbn_db_loss_bwd. */
 int dbn_db_loss_frac_fwd(const float* preds, const float* gts, int N, int H, int W, int channels, float alpha, float beta,
-                         float negative_ratio, float eps, int sum, float* losses, float* coef, void* ws, void* stream);
+                         double negative_ratio, float eps, int sum, float* losses, float* coef, void* ws, void* stream);
 
 /* DBLoss(reduction='none') — true per-pixel OHEM (losses.py:30-39 with a per-pixel BCE): the n_neg largest
  * negative losses are found by a 3-pass radix select on device (no sort, no host sync).  `ws` holds
  * dbn_db_loss_ohem_ws_bytes(N,H,W) bytes (no initialisation required, as above) and must stay untouched between _fwd and _bwd. */
 long dbn_db_loss_ohem_ws_bytes(int N, int H, int W);
 int dbn_db_loss_ohem_fwd(const float* preds, const float* gts, int N, int H, int W, int channels, float alpha, float beta,
-                         float negative_ratio, float eps, float* losses, float* coef, void* ws, void* stream);
+                         double negative_ratio, float eps, float* losses, float* coef, void* ws, void* stream);
 int dbn_db_loss_ohem_bwd(const float* preds, const float* gts, const float* coef, const float* grad_losses, const void* ws,
                          float alpha, float beta, int N, int H, int W, int channels, float* dpreds, void* stream);
 

@@ -41,7 +41,7 @@ def test_ctypes_signatures_match_header():
         if args and args != 'void':
             for a in args.split(','):
                 a = a.strip()
-                kinds += 'p' if '*' in a else 'l' if a.startswith('long') else 'f' if a.startswith('float') else 'i'
+                kinds += 'p' if '*' in a else 'l' if a.startswith('long') else 'f' if a.startswith('float') else 'd' if a.startswith('double') else 'i'
         assert _lib.SIGNATURES[name] == kinds, name
 
 

@@ -46,3 +46,39 @@ def test_pixel_metric_full_size_and_edges():
     assert np.array_equal(rs3.confusion_matrix, np.array([[0, 0], [64, 0]]))
     cal_text_score(torch.ones(1, 8, 8, device=DEV), torch.ones(1, 8, 8, device=DEV), torch.zeros(1, 8, 8, device=DEV), rs3, 0.5)
     assert np.array_equal(rs3.confusion_matrix, np.array([[64, 0], [64, 0]]))
+
+
+@pytest.mark.parametrize('planes', [2, 3])
+@pytest.mark.parametrize('shape', [(3, 7, 9), (2, 33, 31)])
+def test_pixel_confusion_kernel_vs_oracle(shape, planes):
+    """dbn_pixel_confusion through the C ABI against oracle.pixel_confusion, counts bit-exact: odd sizes (one and several workgroups'
+    worth of tail), the probability plane inside 2- and 3-plane predictions (batch_stride), P M exactly at the threshold (strict >:
+    not text), fractional G M below 1 (truncates to background), and two calls accumulating into one histogram."""
+    from gpu_util import L, stream
+    from db_text_minimal_amd import _lib
+    N, H, W = shape
+    thresh = 0.375  # exact in fp32, and so are the products below
+    g = torch.Generator().manual_seed(H)
+    hist = torch.zeros(5, dtype=torch.float64, device=DEV)
+    ref = np.zeros((2, 2))
+    for call in range(2):
+        preds = torch.rand(N, planes, H, W, generator=g)
+        M = torch.randint(0, 3, (N, H, W), generator=g).float() / 2  # 0, 1/2, 1
+        G = torch.randint(0, 3, (N, H, W), generator=g).float() / 2
+        i = torch.arange(N * H * W).view(N, H, W)
+        P = preds[:, 0]
+        P[i % 5 == 0] = 0.375  # at the threshold under M = 1
+        M[i % 5 == 0] = 1.0
+        P[i % 7 == 1] = 0.75  # at the threshold under M = 1/2
+        M[i % 7 == 1] = 0.5
+        P[i % 11 == 2] = float(np.nextafter(np.float32(0.375), np.float32(1)))  # the next float above it
+        M[i % 11 == 2] = 1.0
+        assert int(((P * M) == thresh).sum()) >= 2 * (N * H * W // 7) and int(((G * M > 0) & (G * M < 1)).sum()) > 0
+        ref += O.pixel_confusion(P, G, M, thresh)
+        pd, gd, md = preds.to(DEV), G.to(DEV), M.to(DEV)
+        _lib.check(L().dbn_pixel_confusion(pd.data_ptr(), planes * H * W, gd.data_ptr(), md.data_ptr(), N, H, W, thresh, hist.data_ptr(), stream()),
+                   'pixel_confusion')
+        _, n01, n10, n11, tot = hist.cpu().tolist()
+        got = np.array([[tot - n01 - n10 - n11, n01], [n10, n11]])
+        assert np.array_equal(got, ref), (call, got, ref)
+    assert ref.sum() == 2 * N * H * W and ref[1, 1] > 0 and ref[0, 1] > 0 and ref[1, 0] > 0
