@@ -22,6 +22,7 @@ Every output starts as NaN (an element the kernel never writes fails), and paddi
 import pytest
 import torch
 
+from deform_ref import edge_offsets
 from gpu_util import DEV, DT, ETA, NAN, SR, U, L, col_sum_depth, exact, gen, stream, within
 from db_text_minimal_amd import _lib
 from oracle import dbnet_oracle as O
@@ -329,29 +330,6 @@ def deform_ref(x_nhwc, off_nhwc, stride, rdev):
     x = x_nhwc.to(rdev, torch.float64).permute(0, 3, 1, 2)
     off = off_nhwc[..., :18].to(rdev, torch.float64).permute(0, 3, 1, 2)
     return O.deform_sample(x, off, 3, 3, stride, 1).permute(0, 3, 4, 2, 1)
-
-
-def edge_offsets(N, H, W, stride, g, quarter=True):
-    """Offsets [N, Ho, Wo, 18] that move each tap onto a chosen position class: exactly -1 and exactly H / W (outside), (-1, 0),
-    exactly 0, exactly H - 1 / W - 1, (H - 1, H) / (W - 1, W), interior integers and quarters, far outside (+-(H + 7), +-1000, +-6e4)."""
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-
-    def targets(E, n):
-        cls = torch.tensor([-1.0, -0.75, -0.5, -0.25, 0.0, E - 1.0, E - 0.75, E - 0.5, E - 0.25, float(E), -(E + 7.0), E + 7.0, -1000.0,
-                            1000.0, 6e4, -6e4])
-        t = cls[torch.randint(0, len(cls), (n, ), generator=g)]
-        inner = torch.randint(0, 4 * (E - 1) + 1, (n, ), generator=g).float() / (4 if quarter else 1)
-        return torch.where(torch.rand(n, generator=g) < 0.3, inner, t)
-
-    ho = torch.arange(Ho).view(1, Ho, 1, 1) * stride - 1
-    wo = torch.arange(Wo).view(1, 1, Wo, 1) * stride - 1
-    r = torch.arange(9).view(1, 1, 1, 9) // 3
-    s_ = torch.arange(9).view(1, 1, 1, 9) % 3
-    n = N * Ho * Wo * 9
-    off = torch.empty(N, Ho, Wo, 18)
-    off[..., 0::2] = targets(H, n).view(N, Ho, Wo, 9) - (ho + r)
-    off[..., 1::2] = targets(W, n).view(N, Ho, Wo, 9) - (wo + s_)
-    return off
 
 
 def deform_offsets(kind, at, N, H, W, stride, os_, g):
