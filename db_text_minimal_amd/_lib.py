@@ -248,6 +248,16 @@ class WgradReduceJob(ctypes.Structure):
                 + [('scale', _F), ('smem_bytes', _I)])
 
 
+class PackJob(ctypes.Structure):
+    """One weight panel of dbn_pack_weights_batched's device job table."""
+    _fields_ = [('w', _P), ('out', _P)] + [(f, _I) for f in ('O', 'I', 'R', 'S', 'mode', 'Cs', 'Cd', 'f')]
+
+
+class WinogradPackJob(ctypes.Structure):
+    """One Winograd panel of dbn_winograd_pack_batched's device job table."""
+    _fields_ = [('w', _P), ('out', _P)] + [(f, _I) for f in ('O', 'I', 'Cs', 'dgrad')]
+
+
 class BnbFinal(ctypes.Structure):
     """dbn_bnb_final of include/dbnet_hip.h: the in-kernel finalize of a data gradient's BatchNorm-backward sums."""
     _fields_ = [('counters', _P), ('group', _P), ('c1c2', _P), ('dgamma', _P), ('dbeta', _P), ('c1c2_2', _P), ('dgamma_2', _P),

@@ -16,6 +16,7 @@ Data layout in HBM
     whenever the parameters change.
 """
 import contextlib
+import ctypes
 import os
 
 import torch
@@ -29,6 +30,16 @@ K_STEP_DEFAULT = 50.0
 
 def _p(t):
     return None if t is None else t.data_ptr()
+
+
+def _out_hw(conv, H, W):
+    """Output size of `conv` (k, stride, padding) on an H x W map."""
+    k, s, p = conv.k, conv.stride, conv.padding
+    return (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+
+
+# the eleven BatchNorm arguments of a fused conv epilogue when there is no train-mode BatchNorm behind the conv (see Engine._bn_train_args)
+NO_BN = (None, None, 0.0, 0.0) + (None, ) * 7
 
 
 def flat_layout(numels):
@@ -236,10 +247,14 @@ class Engine:
             self.views[n] = v
             self.grad_views[n] = grad[off:off + p.numel()].view(p.shape)
         self.flat, self.flat_grad, self.offsets = flat, grad, offs
+        self._reset_caches()
+        self.param_epoch += 1
+
+    def _reset_caches(self):
+        """Forget every activation buffer, derived weight and job table (new parameter storage, or another storage type)."""
         self.bufs, self.packs, self.pack_src, self._pack_jobs = {}, {}, {}, None
         self._by_ptr, self._plane_cache = {}, {}
         self._reduce_pending, self._reduce_job_cache, self._reduce_tables = [], {}, {}
-        self.param_epoch += 1
 
     def flush_counters(self):
         """BatchNorm `num_batches_tracked` is bookkeeping only (momentum is fixed); it is
@@ -266,9 +281,7 @@ class Engine:
         'bf16c': the round-1 compute-only mode (fp32 tensors in HBM, operands rounded to bf16 when staged)."""
         ns, at = self.MATH_MODES[mode]
         if at != self.at:  # other storage type: every activation buffer and weight panel is stale
-            self.bufs, self.packs, self.pack_src, self._pack_jobs = {}, {}, {}, None
-            self._by_ptr, self._plane_cache = {}, {}
-            self._reduce_pending, self._reduce_job_cache, self._reduce_tables = [], {}, {}
+            self._reset_caches()
             self.saved_generation = -1
         self.ns, self.at = ns, at
         self.math_mode = mode
@@ -361,6 +374,24 @@ class Engine:
             self._side_used = False
 
     # ------------------------------------------------------------ weight panels
+    def _weight_stamp(self, w, version=None):
+        """What a tensor derived from `w` was made from: w's version counter, the engine's parameter epoch (mark_params_dirty(): the
+        parameters were rewritten through raw pointers) and w's address.  `version` replaces w._version where `w` is itself a derived
+        tensor, rewritten through raw pointers: the stamp's first two entries of the tensor it was derived from, or _folded()'s serial."""
+        return (w._version if version is None else version, self.param_epoch, w.data_ptr())
+
+    def _derived(self, key, stamp, make, fill):
+        """THE cache of derived weights (panels, padded / permuted / folded / combined copies): self.packs[key] = (value, stamp).
+        First use: value = make().  First use or another stamp: fill(value) — a stale value is refilled IN PLACE (the batched repack
+        tables and captured graphs hold its pointers)."""
+        ent = self.packs.get(key)
+        if ent is not None and ent[1] == stamp:
+            return ent[0]
+        value = make() if ent is None else ent[0]
+        fill(value)
+        self.packs[key] = (value, stamp)
+        return value
+
     def pack(self, name, w, mode, stride=1, version=None, cs=0):
         """Weight panels of `w` for (mode, stride), cached until `w` changes.  `version` replaces w._version for tensors
         that are rewritten through raw pointers (the FPN's combined weights).  cs: channels of the source tensor (mode 0)."""
@@ -368,19 +399,19 @@ class Engine:
             self._join_repack()
         ns = self.kind
         key = (name, mode, stride, ns)
-        ent = self.packs.get(key)
-        stamp = (w._version if version is None else version, self.param_epoch, w.data_ptr())
-        if ent is not None and ent[1] == stamp:
-            return ent[0]
         O, I, R, S = w.shape
         cs = cs if mode == 0 else 0
-        if version is None:  # a parameter (not a derived tensor): remembered for the one-launch repack of later steps
-            self.pack_src[key] = (w, cs if cs else (I + 3) // 4 * 4)
-        n = self.L.dbn_igemm_panel_floats_t(ns, O, I, R, S, mode, stride, cs)
-        out = ent[0] if ent is not None else device_empty(n, w.device)
-        check(self.L.dbn_pack_weights_t(ns, w.data_ptr(), O, I, R, S, mode, stride, cs, out.data_ptr(), self.stream), 'pack_weights')
-        self.packs[key] = (out, stamp)
-        return out
+
+        def floats():
+            return self.L.dbn_igemm_panel_floats_t(ns, O, I, R, S, mode, stride, cs)
+
+        def fill(out):
+            if version is None:  # a parameter (not a derived tensor): remembered for the one-launch repack of later steps
+                self.pack_src[key] = (w, cs if cs else (I + 3) // 4 * 4)
+            # (a refill writes the panel the tables and graphs point to: it must still be the size this geometry asks for — cs is not in the key)
+            assert key not in self.packs or out.numel() == floats(), key
+            check(self.L.dbn_pack_weights_t(ns, w.data_ptr(), O, I, R, S, mode, stride, cs, out.data_ptr(), self.stream), 'pack_weights')
+        return self._derived(key, self._weight_stamp(w, version), lambda: device_empty(floats(), w.device), fill)
 
     def _planes(self, t):
         """The pre-split form [3][...] (bf16) of the fp32 activation tensor `t`, made once per step on first use."""
@@ -469,7 +500,6 @@ class Engine:
                     c1c2b = self.fbuf(second[0] + '/bnb_c1c2', 2 * Cd)
                     fin.c1c2_2, fin.dgamma_2, fin.dbeta_2 = (c1c2b.data_ptr(), G[second[0] + '.weight'].data_ptr(),
                                                              G[second[0] + '.bias'].data_ptr())
-            import ctypes
             check(self.L.dbn_igemm_bnsums_t(at, self.ns, srcp, *args[1:], y.data_ptr(), _p(zmask), _p(msc), _p(msh),
                                             self.bufs[bn_name + '/mean'].data_ptr(), self.bufs[bn_name + '/rstd'].data_ptr(),
                                             part.data_ptr(), _p(y2), _p(mean2), _p(rstd2), _p(part2),
@@ -510,35 +540,37 @@ class Engine:
             if key[3] != ns or (beside and key[0] == self.STEM):
                 continue
             ent = self.packs.get(key)
-            stamp = (w._version, self.param_epoch, w.data_ptr())
+            stamp = self._weight_stamp(w)
             if ent is not None and ent[1] != stamp:
                 stale.append((key, w, ent[0], stamp, cs))
         if len(stale) < 8:  # first step (nothing packed yet) or nothing changed: the lazy path handles it
             return
         sig = tuple((k, w.data_ptr(), out.data_ptr()) for k, w, out, _, _ in stale)
         if self._pack_jobs is None or self._pack_jobs[0] != sig:
-            import ctypes
-
-            class Job(ctypes.Structure):
-                _fields_ = [('w', ctypes.c_void_p), ('out', ctypes.c_void_p)] + [(f, ctypes.c_int) for f in
-                                                                                  ('O', 'I', 'R', 'S', 'mode', 'Cs', 'Cd', 'f')]
-            arr = (Job * len(stale))()
+            arr = (_lib.PackJob * len(stale))()
             for i, ((name, mode, stride, _), w, out, _, cs) in enumerate(stale):
                 O, I, R, S = w.shape
-                arr[i] = Job(w.data_ptr(), out.data_ptr(), O, I, R, S, mode, cs if mode == 0 else O,
-                             O if mode == 0 else I, stride if (mode == 1 and stride > 1) else 1)
-            host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-            self._pack_jobs = (sig, host.to(self.flat.device), len(stale))
+                arr[i] = _lib.PackJob(w.data_ptr(), out.data_ptr(), O, I, R, S, mode, cs if mode == 0 else O,
+                                      O if mode == 0 else I, stride if (mode == 1 and stride > 1) else 1)
+            self._pack_jobs = (sig, self._device_table(arr), len(stale))
         _, table, n = self._pack_jobs
-        if beside:
-            with self.side_stream():
-                check(self.L.dbn_pack_weights_batched(table.data_ptr(), n, ns, self.stream), 'pack_weights_batched')
-            self._repack_pending = True
-        else:
-            check(self.L.dbn_pack_weights_batched(table.data_ptr(), n, ns, self.stream), 'pack_weights_batched')
+        self._launch_repack(beside, lambda: check(self.L.dbn_pack_weights_batched(table.data_ptr(), n, ns, self.stream), 'pack_weights_batched'))
         for key, _, out, stamp, _ in stale:
             self.packs[key] = (out, stamp)
         self._repack_winograd(beside)
+
+    def _device_table(self, arr):
+        """A ctypes array of job records as a device byte tensor (what the batched launches read)."""
+        return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.flat.device)
+
+    def _launch_repack(self, beside, launch):
+        """A batched repack launch: on the side stream beside the stem conv (the main stream joins in _join_repack), or inline."""
+        if beside:
+            with self.side_stream():
+                launch()
+            self._repack_pending = True
+        else:
+            launch()
 
     def _repack_fpn(self):
         """The pyramid conv's combined weights (4 launches) and every panel derived from them — forward, data-gradient, Winograd
@@ -554,8 +586,7 @@ class Engine:
             return
         name, conv, Cg = src
         ent = self.packs.get((name, 'combined'))
-        w = conv.weight
-        if ent is None or ent[1] == (w._version, self.param_epoch, w.data_ptr()):
+        if ent is None or ent[1] == self._weight_stamp(conv.weight):
             return
         derived = [k for k in self.packs if isinstance(k[0], str) and k[0].startswith(name + '#') and '#fold' not in k[0]]
 
@@ -583,23 +614,14 @@ class Engine:
             return
         sig = tuple((k, v[0].data_ptr(), v[1].data_ptr()) for k, v in items)
         if self._wino_jobs is None or self._wino_jobs[0] != sig:
-            import ctypes
-
-            class Job(ctypes.Structure):
-                _fields_ = [('w', ctypes.c_void_p), ('out', ctypes.c_void_p)] + [(f, ctypes.c_int) for f in ('O', 'I', 'Cs', 'dgrad')]
-            arr = (Job * len(items))()
+            arr = (_lib.WinogradPackJob * len(items))()
             for i, (_, (w, out, O, I, cs, dgrad)) in enumerate(items):
-                arr[i] = Job(w.data_ptr(), out.data_ptr(), O, I, cs, dgrad)
-            self._wino_jobs = (sig, torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.flat.device), len(items))
+                arr[i] = _lib.WinogradPackJob(w.data_ptr(), out.data_ptr(), O, I, cs, dgrad)
+            self._wino_jobs = (sig, self._device_table(arr), len(items))
         _, table, n = self._wino_jobs
-        if beside:
-            with self.side_stream():
-                check(self.L.dbn_winograd_pack_batched(table.data_ptr(), n, self.stream), 'winograd_pack_batched')
-            self._repack_pending = True
-        else:
-            check(self.L.dbn_winograd_pack_batched(table.data_ptr(), n, self.stream), 'winograd_pack_batched')
+        self._launch_repack(beside, lambda: check(self.L.dbn_winograd_pack_batched(table.data_ptr(), n, self.stream), 'winograd_pack_batched'))
         for k, (w, out, *_r) in items:
-            self.packs[k] = (out, (w._version, self.param_epoch, w.data_ptr()))
+            self.packs[k] = (out, self._weight_stamp(w))
 
     # ------------------------------------------------------------------ kernels
     # 3x3 / stride-1 / pad-1 FORWARD convolutions of the exact-fp32 path through Winograd F(2x2, 3x3) (csrc/winograd_f32.hip): fp32
@@ -618,7 +640,7 @@ class Engine:
         if pl is None:
             L = self.L
             k, s_, p_ = conv.k, conv.stride, conv.padding
-            Ho, Wo = (H + 2 * p_ - k) // s_ + 1, (W + 2 * p_ - k) // s_ + 1
+            Ho, Wo = _out_hw(conv, H, W)
             pl = ConvPlan()
             exact = self.ns == 0 and self.at == 0 and fp32_tensors
             s1 = (k, s_, p_) == (3, 1, 1)
@@ -648,17 +670,13 @@ class Engine:
         if self._repack_pending:  # (first use of a panel the side stream is still rebuilding)
             self._join_repack()
         key = (name, 'winograd', cs, dgrad)
-        ent = self.packs.get(key)
-        stamp = (w._version if version is None else version, self.param_epoch, w.data_ptr())
-        if ent is not None and ent[1] == stamp:
-            return ent[0]
         O, I = (w.shape[1], w.shape[0]) if dgrad else (w.shape[0], w.shape[1])  # channels out of / into THIS conv
-        out = ent[0] if ent is not None else device_empty(self.L.dbn_winograd_panel_floats(O, cs), w.device)
-        if version is None:  # a parameter: remembered for the one-launch refresh after the optimizer step (repack_params)
-            self._wino_src[key] = (w, out, O, I, cs, dgrad)
-        check(self.L.dbn_winograd_pack(w.data_ptr(), O, I, cs, dgrad, out.data_ptr(), self.stream), 'winograd pack ' + name)
-        self.packs[key] = (out, stamp)
-        return out
+
+        def fill(out):
+            if version is None:  # a parameter: remembered for the one-launch refresh after the optimizer step (repack_params)
+                self._wino_src[key] = (w, out, O, I, cs, dgrad)
+            check(self.L.dbn_winograd_pack(w.data_ptr(), O, I, cs, dgrad, out.data_ptr(), self.stream), 'winograd pack ' + name)
+        return self._derived(key, self._weight_stamp(w, version), lambda: device_empty(self.L.dbn_winograd_panel_floats(O, cs), w.device), fill)
 
     def _winograd_conv(self, name, x, conv, y, bn=None, bn_name=None, x_act=None):
         """x_act = (scale, shift): the conv's input is relu(x * scale + shift), applied while the kernel stages its patches (x is the
@@ -671,21 +689,12 @@ class Engine:
             # `step_tflops` counts): the roofline fraction of this kernel is matrix-pipe utilisation, not an effective rate
             # (algorithmic bytes: source + destination once — bench.py: roofline.traffic_over_algorithmic)
             self.prof.begin('winograd_f32_kernel', 2.0 * N * H * W * conv.cout * conv.cin * 4, 4.0 * N * H * W * (C + conv.cout), 'fwd ' + name)
-        if bn is None:
-            check(self.L.dbn_winograd_conv_bn_act_f32(x.data_ptr(), asc, ash, up.data_ptr(), _p(conv.bias), y.data_ptr(), N, H, W, C, conv.cout,
-                                                      None, None, 0.0, 0.0, None, None, None, None, None, None, None, self.stream), 'winograd ' + name)
-            sc = sh = None
-        else:
-            Co = conv.cout
-            sc, sh = self.fbuf(bn_name + '/scale', Co), self.fbuf(bn_name + '/shift', Co)
-            mu, rs = self.fbuf(bn_name + '/mean', Co), self.fbuf(bn_name + '/rstd', Co)
-            ws = self.scratch('_conv_bn_ws', self.L.dbn_winograd_ws_floats(N, H, W, Co))
-            self._announce_bn_final(bn_name, self.L.dbn_winograd_rows(N, H, W), Co)
-            check(self.L.dbn_winograd_conv_bn_act_f32(x.data_ptr(), asc, ash, up.data_ptr(), _p(conv.bias), y.data_ptr(), N, H, W, C, Co,
-                                                      bn.weight.data_ptr(), bn.bias.data_ptr(), bn.eps, bn.momentum,
-                                                      bn.running_mean.data_ptr(), bn.running_var.data_ptr(), sc.data_ptr(), sh.data_ptr(),
-                                                      mu.data_ptr(), rs.data_ptr(), ws.data_ptr(), self.stream), 'winograd+bn ' + name)
-            self.nbt_pending[bn_name] = self.nbt_pending.get(bn_name, 0) + 1
+        sc, sh, bnargs = None, None, NO_BN
+        if bn is not None:
+            sc, sh, bnargs = self._bn_train_args(bn_name, bn, conv.cout, self.L.dbn_winograd_ws_floats(N, H, W, conv.cout))
+            self._announce_bn_final(bn_name, self.L.dbn_winograd_rows(N, H, W), conv.cout)
+        check(self.L.dbn_winograd_conv_bn_act_f32(x.data_ptr(), asc, ash, up.data_ptr(), _p(conv.bias), y.data_ptr(), N, H, W, C, conv.cout,
+                                                  *bnargs, self.stream), ('winograd ' if bn is None else 'winograd+bn ') + name)
         if self.prof:
             self.prof.end()
         return sc, sh
@@ -693,7 +702,7 @@ class Engine:
     def conv_fwd(self, name, x, conv, out_name, version=None, x_act=None):
         N, H, W, C = x.shape
         k, s, p = conv.k, conv.stride, conv.padding
-        Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+        Ho, Wo = _out_hw(conv, H, W)
         assert C >= conv.cin and C % 4 == 0, (name, C, conv.cin)
         if version is None and self._winograd_ok(x, conv):
             y = self.buf(out_name, N, Ho, Wo, conv.cout)
@@ -737,27 +746,31 @@ class Engine:
             self.bufs[bn_name + '/bnf_grp'] = grp
         check(self.L.dbn_conv_bn_set_final(cnt.data_ptr(), grp.data_ptr()), 'conv_bn_set_final')
 
-    def _conv_bn_call(self, what, bn_name, bn, y, args, mode, stride, accumulate=0):
-        """args: dbn_igemm_f32's arguments up to and including `mode` (without accumulate / tile_hint / stream)."""
-        C = y.shape[-1]
+    def _bn_train_args(self, bn_name, bn, C, ws_floats):
+        """(scale, shift, the eleven BatchNorm arguments) of a conv whose epilogue takes the train-mode statistics of `bn`: the coefficient
+        and statistics buffers, the shared scratch of `ws_floats` floats, and one more counted batch (flush_counters).  NO_BN: without."""
         sc, sh = self.fbuf(bn_name + '/scale', C), self.fbuf(bn_name + '/shift', C)
         mu, rs = self.fbuf(bn_name + '/mean', C), self.fbuf(bn_name + '/rstd', C)
-        N, Hd, Wd = y.shape[0], y.shape[1], y.shape[2]
-        ws = self.scratch('_conv_bn_ws', self.L.dbn_conv_bn_ws_floats(N, Hd, Wd, C, mode, stride))
+        ws = self.scratch('_conv_bn_ws', ws_floats)
+        self.nbt_pending[bn_name] = self.nbt_pending.get(bn_name, 0) + 1
+        return sc, sh, (bn.weight.data_ptr(), bn.bias.data_ptr(), bn.eps, bn.momentum, bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+                        sc.data_ptr(), sh.data_ptr(), mu.data_ptr(), rs.data_ptr(), ws.data_ptr())
+
+    def _conv_bn_call(self, what, bn_name, bn, y, args, mode, stride, accumulate=0):
+        """args: dbn_igemm_f32's arguments up to and including `mode` (without accumulate / tile_hint / stream)."""
+        N, Hd, Wd, C = y.shape
+        sc, sh, bnargs = self._bn_train_args(bn_name, bn, C, self.L.dbn_conv_bn_ws_floats(N, Hd, Wd, C, mode, stride))
         at, srcp = self._src(args[0], args[7])
         # args = (src, wpk, bias, dst, N, Hs, Ws, Cs, Hd, Wd, Cd, R, S, stride, pad, mode)
         self._announce_bn_final(bn_name, self.L.dbn_igemm_bn_rows(at, self.ns, *args[4:15], mode, 0), C)
-        check(self.L.dbn_conv_bn_t(at, srcp, *args[1:], accumulate, 0, self.ns, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.eps, bn.momentum,
-                                     bn.running_mean.data_ptr(), bn.running_var.data_ptr(), sc.data_ptr(), sh.data_ptr(),
-                                     mu.data_ptr(), rs.data_ptr(), ws.data_ptr(), self.stream), what)
-        self.nbt_pending[bn_name] = self.nbt_pending.get(bn_name, 0) + 1
+        check(self.L.dbn_conv_bn_t(at, srcp, *args[1:], accumulate, 0, self.ns, *bnargs, self.stream), what)
         return sc, sh
 
     def conv_bn(self, name, x, conv, out_name, bn_name, bn, train, version=None, x_act=None):
         """conv -> BatchNorm coefficients.  Train mode: one fused call (statistics in the conv epilogue)."""
         N, H, W, C = x.shape
         k, s, p = conv.k, conv.stride, conv.padding
-        Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+        Ho, Wo = _out_hw(conv, H, W)
         wino = version is None and self._winograd_ok(x, conv)
         split = self.splitk and self.L.dbn_igemm_splitk_plan_ns(N * Ho * Wo, conv.cout, k * k * C, C, self.ns) > 1
         if not (train and self.fuse_bn_stats) or split:  # split-K convs take their statistics in a (small) separate pass
@@ -790,14 +803,9 @@ class Engine:
 
     def _convt16_panel(self, name, ct):
         w = ct.weight
-        key = (name, 'convt16', self.kind)
-        stamp = (w._version, self.param_epoch, w.data_ptr())
-        ent = self.packs.get(key)
-        if ent is None or ent[1] != stamp:
-            panel = ent[0] if ent is not None else torch.empty(self.L.dbn_convt16_panel_bytes(), device=w.device, dtype=torch.uint8)
-            check(self.L.dbn_convt16_pack(self.kind, w.data_ptr(), panel.data_ptr(), self.stream), 'convt16_pack')
-            self.packs[key] = (panel, stamp)
-        return self.packs[key][0]
+        return self._derived((name, 'convt16', self.kind), self._weight_stamp(w),
+                             lambda: torch.empty(self.L.dbn_convt16_panel_bytes(), device=w.device, dtype=torch.uint8),
+                             lambda panel: check(self.L.dbn_convt16_pack(self.kind, w.data_ptr(), panel.data_ptr(), self.stream), 'convt16_pack'))
 
     head16 = os.environ.get('DBN_HEAD16', '1') == '1'  # inference, 16-bit storage: ConvT -> BN -> ReLU -> ConvT -> sigmoid of both branches in ONE launch
 
@@ -812,18 +820,11 @@ class Engine:
         y = self.buf(out_name, N, 2 * H, 2 * W, ct.cout)
         if self.prof:
             self.prof.begin('convt2x2_b16_kernel<%d>' % self.at, 2.0 * N * H * W * C * ct.cout * 4, float(2 * (x.numel() + y.numel())), 'convT fwd ' + name)
-        sc = sh = None
+        sc, sh, bnargs = None, None, NO_BN
         if bn is not None:
-            sc, sh = self.fbuf(bn_name + '/scale', ct.cout), self.fbuf(bn_name + '/shift', ct.cout)
-            mu, rs = self.fbuf(bn_name + '/mean', ct.cout), self.fbuf(bn_name + '/rstd', ct.cout)
-            ws = self.scratch('_conv_bn_ws', (3 * 64 + 1) * L.dbn_convt16_rows())
-            check(L.dbn_convt16_bn_t(self.at, x.data_ptr(), panel.data_ptr(), _p(ct.bias), y.data_ptr(), N, H, W, bn.weight.data_ptr(),
-                                     bn.bias.data_ptr(), bn.eps, bn.momentum, bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                                     sc.data_ptr(), sh.data_ptr(), mu.data_ptr(), rs.data_ptr(), ws.data_ptr(), self.stream), 'convt16+bn ' + name)
-            self.nbt_pending[bn_name] = self.nbt_pending.get(bn_name, 0) + 1
-        else:
-            check(L.dbn_convt16_bn_t(self.at, x.data_ptr(), panel.data_ptr(), _p(ct.bias), y.data_ptr(), N, H, W, None, None, 0.0, 0.0, None,
-                                     None, None, None, None, None, None, self.stream), 'convt16 ' + name)
+            sc, sh, bnargs = self._bn_train_args(bn_name, bn, ct.cout, (3 * 64 + 1) * L.dbn_convt16_rows())
+        check(L.dbn_convt16_bn_t(self.at, x.data_ptr(), panel.data_ptr(), _p(ct.bias), y.data_ptr(), N, H, W, *bnargs, self.stream),
+              ('convt16 ' if bn is None else 'convt16+bn ') + name)
         if self.prof:
             self.prof.end()
         return y, sc, sh
@@ -888,7 +889,6 @@ class Engine:
         BatchNorm-backward sums of its consumer in the epilogue exactly as _igemm arranges them for the implicit-GEMM kernels.
         panel: a ready Winograd panel mapping dy's channels to dx's (the FPN output conv's level-0 gradient: a forward-form conv
         with the combined weights)."""
-        import ctypes
         N, H, W, O = dy.shape
         Cd = dx.shape[3]
         up = panel if panel is not None else self._winograd_panel(name, conv.weight, O, dgrad=1)
@@ -1024,7 +1024,6 @@ class Engine:
             key = (name, args[:-1])
             job = self._reduce_job_cache.get(key)
             if job is None:
-                import ctypes
                 job = _lib.WgradReduceJob()
                 check(self.L.dbn_wgrad_reduce_describe(*args[:-1], ctypes.byref(job)), 'wgrad reduce describe ' + name)
                 self._reduce_job_cache[key] = job
@@ -1072,13 +1071,11 @@ class Engine:
         sig = tuple(k for k, _ in pending)
         ent = self._reduce_tables.get(sig)
         if ent is None:
-            import ctypes
             arr = (_lib.WgradReduceJob * len(pending))(*[j for _, j in pending])
             first = [0]
             for _, j in pending:
                 first.append(first[-1] + j.blocks)
-            dev = self.flat.device
-            ent = (torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev), torch.tensor(first, dtype=torch.int32, device=dev),
+            ent = (self._device_table(arr), torch.tensor(first, dtype=torch.int32, device=self.flat.device),
                    len(pending), first[-1], max(j.smem_bytes for _, j in pending))
             self._reduce_tables[sig] = ent
         table, first, n, blocks, smem = ent
@@ -1203,19 +1200,18 @@ class Engine:
     def _folded(self, name, conv, bn):
         """(virtual conv with the folded weight / bias, version stamp), re-made when a parameter or a running statistic changed."""
         w = conv.weight
-        stamp = (w._version, self.param_epoch, w.data_ptr(), self.train_forwards, bn.running_mean._version, bn.running_var._version,
-                 bn.weight._version, bn.bias._version)
-        ent = self.packs.get((name, 'fold'))
-        if ent is None or ent[1] != stamp:
-            wf, bf = ent[0][:2] if ent is not None else (device_empty(tuple(w.shape), w.device), device_empty((w.shape[0], ), w.device))
+        stamp = self._weight_stamp(w) + (self.train_forwards, bn.running_mean._version, bn.running_var._version, bn.weight._version,
+                                         bn.bias._version)
+
+        def fill(ent):  # [folded weight, folded bias, serial]
             O = w.shape[0]
             check(self.L.dbn_fold_bn_eval(w.data_ptr(), O, w.numel() // O, _p(conv.bias), bn.weight.data_ptr(), bn.bias.data_ptr(),
-                                          bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.eps, wf.data_ptr(), bf.data_ptr(),
+                                          bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.eps, ent[0].data_ptr(), ent[1].data_ptr(),
                                           self.stream), 'fold_bn_eval ' + name)
             self._fold_count += 1  # (the derived tensors are rewritten through raw pointers: this serial is their version)
-            ent = ((wf, bf, self._fold_count), stamp)
-            self.packs[(name, 'fold')] = ent
-        wf, bf, serial = ent[0]
+            ent[2] = self._fold_count
+        wf, bf, serial = self._derived((name, 'fold'), stamp,
+                                       lambda: [device_empty(tuple(w.shape), w.device), device_empty((w.shape[0], ), w.device), 0], fill)
         return _VirtualConv(conv.cin, conv.cout, conv.k, conv.stride, conv.padding, wf, bf), ('fold', serial)
 
     _fold_count = 0
@@ -1225,21 +1221,17 @@ class Engine:
         vconv, ver = self._folded(name, conv, bn)
         N, H, W, C = x.shape
         k, s, p = conv.k, conv.stride, conv.padding
-        Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+        Ho, Wo = _out_hw(conv, H, W)
         assert C >= conv.cin and C % 4 == 0, (name, C, conv.cin)
         z = self.buf(out_name, N, Ho, Wo, conv.cout)
         assert res is None or (tuple(res.shape) == tuple(z.shape) and res.dtype == z.dtype), name
         if res is None and self.plan(conv, x.shape).pw16:
             # 16-bit storage: a pointwise conv 64 -> 64 | 256 (the FPN lateral on c2) on the ConvT kernel's construction — whole panel in
             # registers, A fragments straight from global memory, no ring (round 5)
-            key = (name, 'pw16', self.kind)
-            ent = self.packs.get(key)
-            stamp = (ver, self.param_epoch, vconv.weight.data_ptr())
-            if ent is None or ent[1] != stamp:
-                panel = ent[0] if ent is not None else torch.empty(self.L.dbn_pw16_panel_bytes(), device=x.device, dtype=torch.uint8)
-                check(self.L.dbn_pw16_pack(self.kind, vconv.weight.data_ptr(), conv.cout, panel.data_ptr(), self.stream), 'pw16_pack')
-                self.packs[key] = (panel, stamp)
-            panel = self.packs[key][0]
+            panel = self._derived((name, 'pw16', self.kind), self._weight_stamp(vconv.weight, ver),
+                                  lambda: torch.empty(self.L.dbn_pw16_panel_bytes(), device=x.device, dtype=torch.uint8),
+                                  lambda pn: check(self.L.dbn_pw16_pack(self.kind, vconv.weight.data_ptr(), conv.cout, pn.data_ptr(), self.stream),
+                                                   'pw16_pack'))
             if self.prof:
                 self.prof.begin('convt2x2_b16_kernel<%d>' % self.at, 2.0 * N * H * W * conv.cout * C, float(2 * (x.numel() + z.numel())), 'fwd ' + name)
             check(self.L.dbn_pw16_act_t(self.at, x.data_ptr(), panel.data_ptr(), vconv.bias.data_ptr(), int(relu), z.data_ptr(), N, H, W,
@@ -1538,15 +1530,10 @@ class Engine:
         x4w = self.buf('x4w', N, H, W, 4) if train else None
         check(L.dbn_nchw3_to_padded4_t(self.at, x.data_ptr(), xp.data_ptr(), _p(x4w), N, H, W, st), 'nchw3_to_padded4')
         w = conv.weight
-        key = ('backbone.conv1', 'stem16', self.kind)
-        stamp = (w._version, self.param_epoch, w.data_ptr())
-        ent = self.packs.get(key)
-        if ent is None or ent[1] != stamp:
-            panel = ent[0] if ent is not None else torch.empty(L.dbn_stem16_panel_bytes(), device=w.device, dtype=torch.uint8)
-            check(L.dbn_stem16_pack(self.kind, w.data_ptr(), panel.data_ptr(), st), 'stem16_pack')
-            self.packs[key] = (panel, stamp)
-        panel = self.packs[key][0]
-        Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        panel = self._derived(('backbone.conv1', 'stem16', self.kind), self._weight_stamp(w),
+                              lambda: torch.empty(L.dbn_stem16_panel_bytes(), device=w.device, dtype=torch.uint8),
+                              lambda pn: check(L.dbn_stem16_pack(self.kind, w.data_ptr(), pn.data_ptr(), st), 'stem16_pack'))
+        Ho, Wo = _out_hw(conv, H, W)
         name = 'backbone.bn1'
         if not train and self.stem16_pool and bool(L.dbn_stem16_pool_eligible(self.at, N, H, W)):
             # inference (round 5): conv + BatchNorm + ReLU + MaxPool2d(3, 2, 1) in ONE launch — the 64-channel conv output never reaches memory
@@ -1566,18 +1553,11 @@ class Engine:
         if self.prof:
             self.prof.begin('stem7x7_b16_kernel<%d>' % self.at, 2.0 * N * Ho * Wo * 64 * 3 * 49, float(2 * (N * Hp * Wp * 4 + N * Ho * Wo * 64)),
                             'fwd backbone.conv1')
+        sc, sh, bnargs = None, None, NO_BN
         if train and self.fuse_bn_stats:
-            sc, sh = self.fbuf(name + '/scale', 64), self.fbuf(name + '/shift', 64)
-            mu, rs = self.fbuf(name + '/mean', 64), self.fbuf(name + '/rstd', 64)
-            ws = self.scratch('_conv_bn_ws', (3 * 64 + 1) * L.dbn_stem16_rows())
-            check(L.dbn_stem16_conv_bn_t(self.at, xp.data_ptr(), panel.data_ptr(), y.data_ptr(), N, H, W, bn.weight.data_ptr(), bn.bias.data_ptr(),
-                                         bn.eps, bn.momentum, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), sc.data_ptr(),
-                                         sh.data_ptr(), mu.data_ptr(), rs.data_ptr(), ws.data_ptr(), st), 'stem16 conv+bn')
-            self.nbt_pending[name] = self.nbt_pending.get(name, 0) + 1
-        else:
-            check(L.dbn_stem16_conv_bn_t(self.at, xp.data_ptr(), panel.data_ptr(), y.data_ptr(), N, H, W, None, None, 0.0, 0.0, None, None,
-                                         None, None, None, None, None, st), 'stem16 conv')
-            sc = sh = None
+            sc, sh, bnargs = self._bn_train_args(name, bn, 64, (3 * 64 + 1) * L.dbn_stem16_rows())
+        check(L.dbn_stem16_conv_bn_t(self.at, xp.data_ptr(), panel.data_ptr(), y.data_ptr(), N, H, W, *bnargs, st),
+              'stem16 conv' if sc is None else 'stem16 conv+bn')
         if self.prof:
             self.prof.end()
         if sc is None:
@@ -1589,28 +1569,22 @@ class Engine:
         """conv2_offset has 18 output channels; the GEMM kernels want multiples of 64: zero-padded copy of its
         weight/bias (the offsets then live in channels 0..17 of a 64-channel map)."""
         w = oc.weight
-        stamp = (w._version, self.param_epoch, w.data_ptr())
-        ent = self.packs.get((name, 'pad64'))
-        if ent is None or ent[1] != stamp:
-            wp, bp = ent[0] if ent is not None else (torch.zeros(64, oc.cin, oc.k, oc.k, device=w.device),
-                                                     torch.zeros(64, device=w.device))
-            wp[:w.shape[0]].copy_(w.detach())
-            bp[:w.shape[0]].copy_(oc.bias.detach())
-            self.packs[(name, 'pad64')] = ((wp, bp), stamp)
-        wp, bp = self.packs[(name, 'pad64')][0]
+        stamp = self._weight_stamp(w)
+
+        def fill(padded):
+            padded[0][:w.shape[0]].copy_(w.detach())
+            padded[1][:w.shape[0]].copy_(oc.bias.detach())
+        wp, bp = self._derived((name, 'pad64'), stamp, lambda: (torch.zeros(64, oc.cin, oc.k, oc.k, device=w.device),
+                                                                torch.zeros(64, device=w.device)), fill)
         return _VirtualConv(oc.cin, 64, oc.k, oc.stride, oc.padding, wp, bp), stamp[:2]
 
     def _cols_conv(self, name, conv):
         """The deformable conv's weight [O,C,3,3] as the 1x1 conv [O, 9C] over the sampled columns ((tap, channel) order)."""
         w = conv.weight
-        stamp = (w._version, self.param_epoch, w.data_ptr())
-        ent = self.packs.get((name, 'ohwi'))
-        if ent is None or ent[1] != stamp:
-            wp = ent[0] if ent is not None else device_empty((conv.cout, conv.k * conv.k * conv.cin, 1, 1), w.device)
-            check(self.L.dbn_permute_weight(w.data_ptr(), wp.data_ptr(), conv.cout, conv.cin, conv.k * conv.k, 1, 1.0, self.stream),
-                  'permute_weight')
-            self.packs[(name, 'ohwi')] = (wp, stamp)
-        wp = self.packs[(name, 'ohwi')][0]
+        stamp = self._weight_stamp(w)
+        wp = self._derived((name, 'ohwi'), stamp, lambda: device_empty((conv.cout, conv.k * conv.k * conv.cin, 1, 1), w.device),
+                           lambda t: check(self.L.dbn_permute_weight(w.data_ptr(), t.data_ptr(), conv.cout, conv.cin, conv.k * conv.k, 1, 1.0,
+                                                                     self.stream), 'permute_weight'))
         return _VirtualConv(conv.k * conv.k * conv.cin, conv.cout, 1, 1, 0, wp, None), stamp[:2]
 
     def _deform_conv_bn(self, name, x, blk, out_name, bn_name, bn, train):
@@ -1757,7 +1731,7 @@ class Engine:
             if not self._fold_ok(cur, conv, False):
                 return None
             N, H, W, _ = cur.shape
-            cur = _Shape(N, (H + 2 * conv.padding - conv.k) // conv.stride + 1, (W + 2 * conv.padding - conv.k) // conv.stride + 1, conv.cout)
+            cur = _Shape(N, *_out_hw(conv, H, W), conv.cout)
         if blk.downsample is not None and not self._fold_ok(x, blk.downsample[0], False):
             return None
         cur, res = x, x
@@ -2089,15 +2063,15 @@ class Engine:
         Co = w.shape[0]
         if version is None:
             self._fpn_src = (name, conv, Cg)
-        stamp = (w._version if version is None else version, self.param_epoch, w.data_ptr())
-        ent = self.packs.get((name, 'combined'))
-        if ent is None or ent[1] != stamp:
-            wds = ent[0] if ent is not None else [device_empty((Cg, Co, (1 << g) + 2, (1 << g) + 2), w.device) for g in range(4)]
+        stamp = self._weight_stamp(w, version)
+
+        def fill(wds):
             for g in range(4):
                 check(self.L.dbn_fpn_combine_weights(w.data_ptr(), Co, w.shape[1], g, Cg, wds[g].data_ptr(), self.stream),
                       'fpn_combine_weights')
-            self.packs[(name, 'combined')] = (wds, stamp)
-        return self.packs[(name, 'combined')][0], stamp[:2]
+        wds = self._derived((name, 'combined'), stamp,
+                            lambda: [device_empty((Cg, Co, (1 << g) + 2, (1 << g) + 2), w.device) for g in range(4)], fill)
+        return wds, stamp[:2]
 
     def _fpn_conv_forward(self, name, conv, zs, out_name, bn_name, bn, train):
         N, H, W, Cg = zs[0].shape
@@ -2129,8 +2103,8 @@ class Engine:
                 up = self._winograd_panel(name + '#lv0', wds[0], Cg, dgrad=1, version=wver)
                 if self.prof:
                     self.prof.begin('winograd_f32_kernel', 2.0 * N * H * W * Co * Cg * 4, 4.0 * N * H * W * (Co + Cg), 'fwd %s level 0' % name)
-                check(self.L.dbn_winograd_conv_bn_f32(zs[0].data_ptr(), up.data_ptr(), _p(conv.bias), y.data_ptr(), N, H, W, Cg, Co, None, None,
-                                                      0.0, 0.0, None, None, None, None, None, None, None, self.stream), 'winograd ' + name)
+                check(self.L.dbn_winograd_conv_bn_f32(zs[0].data_ptr(), up.data_ptr(), _p(conv.bias), y.data_ptr(), N, H, W, Cg, Co, *NO_BN,
+                                                      self.stream), 'winograd ' + name)
                 if self.prof:
                     self.prof.end()
             flops = sum(2.0 * N * z.shape[1] * z.shape[2] * Cg * Co * ((1 << g) + 2)**2 for g, z in enumerate(zs) if g >= first)
@@ -2139,16 +2113,9 @@ class Engine:
                 waves = '1,4' if (not self._use_planes and self.at in (1, 2) and self.ns == 1) else '2,2'
                 self.prof.begin('igemm_f32_kernel<128,%d,%s,3,%d,%d,false,0,true>' % (bn_tile, waves, self.ns, 3 if self._use_planes else self.at), flops, 0.0,
                                 'fwd %s (pyramid)' % name)
+            bnargs = NO_BN
             if fused:
-                C = Co
-                sc, sh = self.fbuf(bn_name + '/scale', C), self.fbuf(bn_name + '/shift', C)
-                mu, rs = self.fbuf(bn_name + '/mean', C), self.fbuf(bn_name + '/rstd', C)
-                ws = self.scratch('_conv_bn_ws', self.L.dbn_pyramid_conv_ws_floats(N, H, W, Co))
-                bnargs = (bn.weight.data_ptr(), bn.bias.data_ptr(), bn.eps, bn.momentum, bn.running_mean.data_ptr(),
-                          bn.running_var.data_ptr(), sc.data_ptr(), sh.data_ptr(), mu.data_ptr(), rs.data_ptr(), ws.data_ptr())
-                self.nbt_pending[bn_name] = self.nbt_pending.get(bn_name, 0) + 1
-            else:
-                bnargs = (None, None, 0.0, 0.0) + (None, ) * 7
+                sc, sh, bnargs = self._bn_train_args(bn_name, bn, Co, self.L.dbn_pyramid_conv_ws_floats(N, H, W, Co))
             pat, zp = self.at, [z.data_ptr() for z in zs]
             if self._use_planes and Cg % 16 == 0:
                 pat, zp = 3, [self._planes(z).data_ptr() for z in zs]
