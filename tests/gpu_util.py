@@ -105,6 +105,18 @@ def wgrad(sm, big, O, I, k, stride, pad, scale=1.0, ns=0):
     return g
 
 
+def wgrad_t(sm, big, O, I, k, stride, pad, ns=0, scale=1.0):
+    """dbn_wgrad_t on fp32 / bf16 tensors (sm: the output-side tensor [N, Ho, Wo, O], big: the input side [N, H, W, Cb]) with a NaN-filled
+    slab and gradient."""
+    N, Ho, Wo, _ = sm.shape
+    _, H, W, Cb = big.shape
+    slab = torch.full((L().dbn_wgrad_slab_floats_hw(N, Ho, Wo, O, H, W, Cb, k, k, big.element_size()), ), float('nan'), device=DEV)
+    g = torch.full((O, I, k, k), float('nan'), device=DEV)
+    _lib.check(L().dbn_wgrad_t(AT_OF[big.dtype], ns, sm.data_ptr(), big.data_ptr(), slab.data_ptr(), g.data_ptr(), N, Ho, Wo, O, H, W, Cb, I, k, k,
+                               stride, pad, scale, stream()), 'wgrad_t')
+    return g
+
+
 def reduce_ws():
     return torch.empty(L().dbn_reduce_ws_floats(512), device=DEV)
 
