@@ -33,11 +33,10 @@ struct ConvT16Params {
 
 constexpr int CT_PITCH = 64 + 8;
 
+// waves per SIMD the register allocation aims at: the ConvT and the 64 -> 256 conv two (256 registers, five weight fragments live in scratch;
+// one wave, none spilled, was the alternative: DESIGN 30)
 template <int AT, int PW = 0>  // PW: 0 = the ConvT; 1 / 4 = pointwise conv 64 -> 64 * PW
-#ifndef DBN_CT16_WPE
-#define DBN_CT16_WPE 2  // waves per SIMD the register allocation aims at (2: 256 registers, five weight fragments live in scratch; 1: none spilled)
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PW == 1 ? 4 : DBN_CT16_WPE, PW == 1 ? 4 : DBN_CT16_WPE))) void convt2x2_b16_kernel(const ConvT16Params p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PW == 1 ? 4 : 2, PW == 1 ? 4 : 2))) void convt2x2_b16_kernel(const ConvT16Params p) {
     static_assert(AT == 1 || AT == 2, "16-bit storage");
     __shared__ unsigned short smem[4 * 32 * CT_PITCH];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);

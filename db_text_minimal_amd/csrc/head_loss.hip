@@ -41,23 +41,13 @@ __device__ __forceinline__ float group16_sum(float v) {
     v += dpp_f32<DPP_ROW_MIRROR>(v);        // lane i <-> 15-i: the other half
     return v;
 }
-// value of lane `k` (0..3) of this lane's quad
-#ifndef DBN_HT_NODPP
-#define DBN_HT_NODPP 0  // 1 (A/B build, tools/cotenancy_diff.py): the quad broadcasts of head_tail_bwd through ds_bpermute instead of DPP
-#endif
 #ifndef DBN_HT_CHECK
 #define DBN_HT_CHECK 0  // 1 (A/B build): head_tail_bwd_kernel re-loads its loop-invariant operands at the end and counts the lanes whose registers differ
 #endif
-#ifndef DBN_HT_WAVES
-#define DBN_HT_WAVES 0  // n > 0 (A/B build): head_tail_bwd_kernel compiled for n waves per SIMD (register budget 512 / n)
-#endif
+// value of lane `k` (0..3) of this lane's quad
 template <int K>
 __device__ __forceinline__ float quad_bcast(float v) {
-#if DBN_HT_NODPP
-    return __shfl(v, (int)((threadIdx.x & 63u & ~3u) | K), 64);
-#else
     return dpp_f32<K | (K << 2) | (K << 4) | (K << 6)>(v);
-#endif
 }
 
 __device__ __forceinline__ float group8_sum(float v) {
@@ -191,18 +181,10 @@ __global__ __launch_bounds__(256) void head_tail_fwd_kernel(const void* __restri
 // Backward.  For each quarter pixel: dl_b[ab], dl_t[ab] (grad wrt the two logits) from
 // dpreds and the saved maps; dxb = sum_ab dl_b[ab]*wb[ci][ab]; dwb[ci][ab] += xb[ci]*dl_b[ab].
 // part: [grid][2*(256+1)] block partials of (dwb[64*4], dbias_b, dwt[64*4], dbias_t).
-#if DBN_HT_WAVES
-#define DBN_HT_OCC __attribute__((amdgpu_waves_per_eu(DBN_HT_WAVES, DBN_HT_WAVES)))
-#else
-#define DBN_HT_OCC
-#endif
 // STORE = false (dbn_head_tail_bn_bwd_t): the two gradients are not written (dxb / dxt unused) — the partial rows are the same bits.
-// U: pixels whose loads are in flight together (1: the loop as it always was).
-#ifndef DBN_HT_SUMS_UNROLL
-#define DBN_HT_SUMS_UNROLL 2  // U of the store-free form (A/B builds: 1, 4, 8)
-#endif
+// U: pixels whose loads are in flight together (1: the loop as it always was; the store-free form runs with 2).
 template <int AT, bool STORE = true, int U = 1>
-__global__ __launch_bounds__(256) DBN_HT_OCC void head_tail_bwd_kernel(const void* __restrict__ xb, const void* __restrict__ xt, const float* __restrict__ wb,
+__global__ __launch_bounds__(256) void head_tail_bwd_kernel(const void* __restrict__ xb, const void* __restrict__ xt, const float* __restrict__ wb,
                                      const float* __restrict__ wt, const float* __restrict__ preds,
                                      const float* __restrict__ dpreds, const float* __restrict__ sc_b,
                                      const float* __restrict__ sh_b, const float* __restrict__ sc_t,
@@ -1154,7 +1136,7 @@ int dbn_head_tail_bn_bwd_t(int at, int phases, const void* yb, const void* yt, c
     float* sums = ws + HEAD_BN_WS_SUMS;
     float* cc = ws + HEAD_BN_WS_CC;
     if (phases & 1) {
-        DBN_DISPATCH_AT(at, hipLaunchKernelGGL((head_tail_bwd_kernel<AT, false, DBN_HT_SUMS_UNROLL>), dim3(nb), dim3(256), 0, st, yb, yt, wb, wt, preds, dpreds, bn_scale_b,
+        DBN_DISPATCH_AT(at, hipLaunchKernelGGL((head_tail_bwd_kernel<AT, false, 2>), dim3(nb), dim3(256), 0, st, yb, yt, wb, wt, preds, dpreds, bn_scale_b,
                                                bn_shift_b, bn_scale_t, bn_shift_t, bn_mean_b, bn_rstd_b, bn_mean_t, bn_rstd_t, (void*)nullptr,
                                                (void*)nullptr, ws, N, Hq, Wq, channels, kstep));
         hipLaunchKernelGGL(fold_head_grads_kernel, dim3(dbn_ceil_div(2 * 257, 8)), dim3(256), 0, st, ws, nb, dw_b, dbias_b, dw_t, dbias_t,

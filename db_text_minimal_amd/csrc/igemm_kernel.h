@@ -22,7 +22,7 @@ namespace {
 // Register budget: the 128x128 fp32 tile needs 88 VGPR + 64 AGPR = 3 waves per SIMD.  Asking for 4 waves
 // (amdgpu_waves_per_eu) makes the compiler fit it into the unified 128 registers; with a prefetch distance of one k-tile
 // that cost 4 spills and gave +1.6 % on large launches, with the second register set of the two-tile prefetch it spills 56
-// and loses 35 % — the experiment (round 1-2: DBN_IGEMM_W4) was removed in round 3.
+// and loses 35 %.
 // pixel-patch kernels with three planes: two waves per SIMD (<= 256 registers; the fully unrolled nine stages had taken 257)
 // exact-fp32 16K-element tiles with the BatchNorm-backward epilogue (EPI = 1): three waves per SIMD like the plain kernel (the row
 // sweep of that epilogue peaks 1-3 registers above the 104 that three waves allow; the attribute makes the allocator fit it)
@@ -57,10 +57,7 @@ __global__ __launch_bounds__(WM* WN * 64) DBN_IGEMM_OCC(BM, BN, NS, MODE, PATCH,
     constexpr int MI = TM / 32, NI = TN / 32;
     constexpr int ES = AT == 0 ? 4 : 2;            // bytes per stored source element
     constexpr bool DST_F32 = AT == 0 || AT == 3;
-#ifndef DBN_BUFST
-#define DBN_BUFST 1
-#endif
-    constexpr bool BUFST = DBN_BUFST && DST_F32 && MODE < 2;  // plain epilogue through raw buffer stores (see the end of the kernel)
+    constexpr bool BUFST = DST_F32 && MODE < 2;  // plain epilogue through raw buffer stores (see the end of the kernel)
     constexpr int NP = AT == 3 ? 3 : 1;            // 16-bit planes of the source
     constexpr int A_SH = AT == 0 ? 2 : 1;          // pieces per row and plane = 1 << A_SH (4 x 4 fp32 channels, or 2 x 8 16-bit channels)
     constexpr int A_CH = AT == 0 ? 4 : 8;          // channels per 16-byte piece
@@ -79,21 +76,13 @@ __global__ __launch_bounds__(WM* WN * 64) DBN_IGEMM_OCC(BM, BN, NS, MODE, PATCH,
     // in native bf16; 51 KB of LDS and a second register set of 4 units cost occupancy, and the barrier was not what bounds them —
     // the instruction stream per unit is).  Every path runs with one unit per barrier.
     constexpr int KU = 1;
-#ifndef DBN_DIRECTB
-#define DBN_DIRECTB 1
-#endif
     // DIRECTB (exact fp32 on fp32 tensors; round 3): the weight panel's pieces are fetched in MFMA-fragment order straight into
     // registers — lane (li, lh) of wave column wn needs chunk 2*s2 + lh of column wn*TN + b*32 + li: 16 contiguous bytes of the packed
     // panel, a half-wave 512 — one k-tile ahead: no LDS image, no ds_write / ds_read for B, half the LDS footprint (64 x 64 tile:
     // 8.4 KB).  The two waves of a wave column fetch the same pieces (the second from L1).  Same products in the same order.
-    // Measured (interleaved A/B on one box, -DDBN_DIRECTB=0 is the staged form): the kernels alone within 1 % either way, the
-    // two-stream step +0.6 ... +0.9 % (538.2 / 541.8 against 534.8 / 536.9 images/s) — the smaller footprint co-resides better with
-    // the weight-gradient stream's workgroups.
-// (also for the bf16 matrix modes on fp32 tensors — fragment = slice lh of plane t of the pre-split panel: bf16x3 739 -> 749 images/s)
-#ifndef DBN_DIRECTB_NS
-#define DBN_DIRECTB_NS 1
-#endif
-    constexpr bool DIRECTB = DBN_DIRECTB && (NS == 0 || DBN_DIRECTB_NS) && AT == 0 && !PATCH;
+    // Also for the bf16 matrix modes on fp32 tensors: fragment = slice lh of plane t of the pre-split panel.  The staged form measured
+    // equal on the kernels alone and slower on the two-stream step.
+    constexpr bool DIRECTB = AT == 0 && !PATCH;
     constexpr int NF = NS == 0 ? 2 : NS;  // B fragments (16 bytes each) per accumulator column block and k-tile
     constexpr int UNIT = A_IMG + (DIRECTB ? 0 : B_IMG);
     constexpr int STAGE = KU * UNIT;
@@ -101,53 +90,30 @@ __global__ __launch_bounds__(WM* WN * 64) DBN_IGEMM_OCC(BM, BN, NS, MODE, PATCH,
     static_assert(A_LD >= 1 && B_LD >= 1, "tile too small for the workgroup");
     // 16-bit storage (AT != 0): LDS-DMA ring (see the main loop): stages of DMA_SU units, unpadded images [plane][k/8][row]
     constexpr int DMA_SU = 2;
-#ifndef DBN_DBG16
-#define DBN_DBG16 0  // profile by deletion of the 16-bit ring loop (tools/flavour.sh <name> conv_b16.hip "-DDBN_DBG16=<bits>"; timing only, wrong results): 1 no per-instruction address arithmetic, 2 no weight-fragment loads, 4 no LDS fragment reads, 8 no A DMA
-#endif
-#ifndef DBN_DIRECTB16
-#define DBN_DIRECTB16 1
-#endif
-    // DB16 (stored 16-bit operands, generic ring, not the pyramid form; round 3): the weight fragments come straight from the packed
+    // DB16 (stored 16-bit operands, generic ring; round 3): the weight fragments come straight from the packed
     // panel into registers, one stage ahead (as DIRECTB for fp32) — the ring carries the A panel only: half the DMA instructions and
-    // their scalar bookkeeping, no fragment reads for B, a ring half the size.  bf16 step 1624 -> 1683 images/s (interleaved A/B on
-    // one box; -DDBN_DIRECTB16=0 builds the ring with both panels)
-#ifndef DBN_DIRECTB16_PYR
-#define DBN_DIRECTB16_PYR 1  // round 5: ... and the pyramid form (MODE 3) too: its ring is bound by the bytes it can keep in flight
-#endif
-    constexpr bool DB16 = DBN_DIRECTB16 && AT != 0 && AT != 3 && (MODE != 3 || DBN_DIRECTB16_PYR) && !PATCH;
+    // their scalar bookkeeping, no fragment reads for B, a ring half the size.  Since round 5 the pyramid form (MODE 3) too: its ring
+    // is bound by the bytes it can keep in flight.  The ring with both panels measured slower.
+    constexpr bool DB16 = AT != 0 && AT != 3 && !PATCH;
     constexpr int DMA_UNIT = NP * 2 * BM + (DB16 ? 0 : NSX * 2 * BN);  // 16-byte slots of one unit
     constexpr int DMA_STAGE = DMA_SU * DMA_UNIT;
-#ifndef DBN_PYR_NSTG
-#define DBN_PYR_NSTG 4  // ring depth of the register-fed pyramid form (A panel only: 8 KB per stage at 128 rows).  6 (48 KB, still three workgroups per CU) measured equal: cfg5 14.55 / 14.50 vs 14.56 / 14.59 ms, bf16 step 1660 / 1671 vs 1665 / 1664 images/s
-#endif
-#ifndef DBN_PYR_NSTG_WIDE
-#define DBN_PYR_NSTG_WIDE 4  // ... and of its 128 x 256 tile (round 6; two workgroups per CU, the ring inside the 64 KB epilogue region)
-#endif
-    constexpr int DMA_NSTG = (DB16 && MODE == 3 && BN == 256 && DMA_STAGE * 16 * DBN_PYR_NSTG_WIDE <= 64 * 1024) ? DBN_PYR_NSTG_WIDE :
-                             (DB16 && MODE == 3 && DMA_STAGE * 16 * DBN_PYR_NSTG <= 48 * 1024) ? DBN_PYR_NSTG :
-                             DMA_STAGE * 16 * 4 <= 64 * 1024 ? 4 : DMA_STAGE * 16 * 3 <= 160 * 1024 ? 3 : 2;
+    // ring depth: four stages where they fit 64 KB — the register-fed pyramid form (A panel only: 8 KB per stage at 128 rows) and its
+    // 128 x 256 tile always do; six stages measured equal there
+    constexpr int DMA_NSTG = DMA_STAGE * 16 * 4 <= 64 * 1024 ? 4 : DMA_STAGE * 16 * 3 <= 160 * 1024 ? 3 : 2;
     // PATCH: two patch buffers [plane][4 k/8 slices][10 x 18 pixels] + a ring of P_NSTG weight stages of two units
     constexpr int P_PATCH = NSX * 4 * 180;
     constexpr int P_BUNIT = NSX * 2 * BN, P_BSTAGE = 2 * P_BUNIT;
-#ifndef DBN_P_NSTG
-#define DBN_P_NSTG 4  // weight-ring depth of the single-plane pixel-patch kernels (A/B build; round 5: 6 / 8 stages — fewer workgroups per CU — are slower: cfg5 12.29 -> 12.52 / 12.56 ms, bf16 step 1704 -> 1687 / 1642 images/s)
-#endif
-    constexpr int P_NSTG = NSX == 1 ? DBN_P_NSTG : 3;
+    constexpr int P_NSTG = NSX == 1 ? 4 : 3;  // (single plane: 6 / 8 stages leave fewer workgroups per CU and measured slower)
     // three planes: ONE patch buffer (refilled between two barriers at a channel-block boundary) keeps the workgroup at 70 KB
     // so that two fit a CU; with a second buffer it was alone on its CU (103 KB, one wave per SIMD: every LDS latency exposed)
     constexpr int P_NBUF = NSX == 1 ? 2 : 1;
     // (EPI = 1 on fp32 storage: the row-major epilogue needs half a tile — a whole one for one accumulator block per wave — of fp32)
-#ifndef DBN_DIRECTBP
-#define DBN_DIRECTBP 1
-#endif
     // DBP (pixel-patch kernels of the three-plane bf16x3 mode; round 3): the weight fragments straight into registers, one stage (two
     // taps) ahead — no weight ring, and the only barriers left are the two around a patch refill (one channel block = 18 units
     // between them).  Measured (interleaved A/B on one box): bf16x3 714 -> 732 images/s; the single-plane kernels (bf16 storage,
-    // two patch buffers, ten barriers per block that also pace the ring) lose with it: 1644 -> 1620 — they keep the ring.
-#ifndef DBN_DBP_NS1
-#define DBN_DBP_NS1 0  // 1: the single-plane (bf16 / fp16) pixel-patch kernels too (A/B build; round 5 again: cfg5 14.22 / 14.20 vs 14.21 / 14.23 ms, bf16 step 1677 / 1677 vs 1662 / 1652 images/s: the ring stays)
-#endif
-    constexpr bool DBP = DBN_DIRECTBP && PATCH && (NS == 3 || (DBN_DBP_NS1 && NS == 1));
+    // two patch buffers, ten barriers per block that also pace the ring) lose with it: 1644 -> 1620 — they keep the ring (measured
+    // again in round 5).
+    constexpr bool DBP = PATCH && NS == 3;
     constexpr int LOOP_SMEM = PATCH ? P_NBUF * P_PATCH + ((DBP || NS == 0) ? 0 : P_NSTG * P_BSTAGE) : AT != 0 ? DMA_NSTG * DMA_STAGE : 2 * STAGE;
     constexpr int EPI_SMEM = (EPI == 1 && DST_F32) ? BM * BN / (4 * (MI >= 2 ? 2 : 1)) : 0;
     // (16-bit destinations: the output tile is staged through LDS, BM rows of BN + 8 elements)
@@ -1020,11 +986,6 @@ __global__ __launch_bounds__(WM* WN * 64) DBN_IGEMM_OCC(BM, BN, NS, MODE, PATCH,
             const int tcb = fixed ? ucb[uc] : (uw ? ucb[DMA_SU - 1] : ucb[0]), tkt = fixed ? ukt[uc] : (uw ? ukt[DMA_SU - 1] : ukt[0]);
             auto* dst = (__attribute__((address_space(3))) void*)(smem + slot * DMA_STAGE + u * DMA_UNIT + i_lds[i]);
             if (isA) {
-                if constexpr ((DBN_DBG16 & 1) != 0) {  // profile by deletion (timing only): no tap / bounds / offset arithmetic per DMA instruction
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, dst, 16, (int)(i_add[i] + (unsigned)r_nb[i] * 2u + (unsigned)u * 4096u), 0, 0, 0);
-                    continue;
-                }
-                if constexpr ((DBN_DBG16 & 8) != 0) continue;  // no A DMA at all
                 const int hs = MODE == 0 ? r_hb[i] + tr : r_hb[i] - tr;
                 const int ws = MODE == 0 ? r_wb[i] + ts : r_wb[i] - ts;
                 const bool v = v_u && (unsigned)hs < (unsigned)gHs && (unsigned)ws < (unsigned)gWs;
@@ -1079,10 +1040,6 @@ __global__ __launch_bounds__(WM* WN * 64) DBN_IGEMM_OCC(BM, BN, NS, MODE, PATCH,
 #pragma unroll
                     for (int b = 0; b < NI; ++b) {
                         typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-                        if constexpr ((DBN_DBG16 & 2) != 0) {  // (deletion: no weight-fragment loads)
-                            rbB[st__][u][t][b] = f32x4{1.f, 2.f, 3.f, (float)so};
-                            continue;
-                        }
                         const u32x4_ v_ = __builtin_amdgcn_raw_buffer_load_b128(rsrcB, (int)bvo[t][b], (int)so, 0);
                         rbB[st__][u][t][b] = __builtin_bit_cast(f32x4, v_);
                     }
@@ -1094,7 +1051,7 @@ __global__ __launch_bounds__(WM* WN * 64) DBN_IGEMM_OCC(BM, BN, NS, MODE, PATCH,
         // prologue: the first DMA_NSTG - 1 stages of A, then the first TWO B sets (no dummy register loads: the compiler deletes loads
         // whose results are overwritten, and the counted waits below must match what is really in flight).
         // Round 6: the weight fragments of stage s are fetched at stage s - 2 (three register sets, the loop unrolled by three).  Profile
-        // by deletion (-DDBN_DBG16=2, configs[4]): without the fragment loads the pyramid launch is a third shorter — fetched ONE stage
+        // by deletion (configs[4]): without the fragment loads the pyramid launch is a third shorter — fetched ONE stage
         // ahead (rounds 3-5) a set had one stage time, about a microsecond, to come back from L2, and every stage ended up waiting for it.
 #pragma unroll
         for (int s_ = 0; s_ < DMA_NSTG - 1; ++s_) issue_stage(s_);
@@ -1110,7 +1067,7 @@ __global__ __launch_bounds__(WM* WN * 64) DBN_IGEMM_OCC(BM, BN, NS, MODE, PATCH,
         // the first stages have more behind them (the prologue's order), for which the same count is merely stricter than needed.
         auto body = [&](auto SET, auto EARLY) {
             constexpr int set = decltype(SET)::value;
-            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(((DBN_DBG16 & 8) ? 0 : (DMA_NSTG - 2) * PW) + ((DBN_DBG16 & 2) ? 0 : NB * 2)) : "memory");
+            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((DMA_NSTG - 2) * PW + NB * 2) : "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             issue_bs(std::integral_constant<int, (set + 2) % 3>{});
@@ -1127,7 +1084,7 @@ __global__ __launch_bounds__(WM* WN * 64) DBN_IGEMM_OCC(BM, BN, NS, MODE, PATCH,
                 for (int t = 0; t < NSX; ++t) {
 #pragma unroll
                     for (int a = 0; a < MI; ++a)
-                        af[t][a] = (DBN_DBG16 & 4) ? __builtin_bit_cast(bf16x8, rbB[set][u][t][a % NI]) : __builtin_bit_cast(bf16x8, As[(t * BM + wm * TM + a * 32 + li) * 2 + lh]);
+                        af[t][a] = __builtin_bit_cast(bf16x8, As[(t * BM + wm * TM + a * 32 + li) * 2 + lh]);
 #pragma unroll
                     for (int b = 0; b < NI; ++b) bf[t][b] = __builtin_bit_cast(bf16x8, rbB[set][u][t][b]);
                 }
@@ -2051,13 +2008,10 @@ int launch_igemm_ns(IgemmParams& p, int mode, hipStream_t st) {
 // every row count of the host side are unchanged; per output element the same products in the same order: bit-identical results.
 // dbn_g_wide_tile (conv.hip, dbn_set_pyramid_wide): 0 off, 1 the pyramid form, 2 also plain forward / stride-1 data-gradient launches,
 // 3 as 2 whatever the launch's size.
-#ifndef DBN_WIDE_WM
-#define DBN_WIDE_WM 1  // wave layout of the wide tile: 1 x 4 waves of 128 x 64 — no two waves load the same weight fragments (the register-fed B side is
-                       // 28 GB per configs[4] launch with 2 x 2 waves of 64 x 128, half of it with 1 x 4): configs[4] 10.95 -> 10.74 ms per forward
-#endif
 template <int AT>
 int launch_wide(IgemmParams& p, int mode, hipStream_t st) {
-    constexpr int WM_ = DBN_WIDE_WM, WN_ = 4 / DBN_WIDE_WM;
+    // 1 x 4 waves of 128 x 64: no two waves load the same weight fragments; 2 x 2 measured slower, DESIGN 30
+    constexpr int WM_ = 1, WN_ = 4;
     static_assert(AT == 1 || AT == 2, "16-bit storage");
     const int rows = mode == 3 ? 64 * dbn_ceil_div(p.N * (p.Hdf >> 3) * (p.Wdf >> 3), 128) : dbn_ceil_div(p.N * p.Hdf * p.Wdf, 128);
     int grid = rows * (p.Cd / 256);
@@ -2082,10 +2036,6 @@ static inline bool wide_tile_ok(const IgemmParams& p, int mode) {  // (the size 
     return dbn_wide_tile_geom_ok(mode, p.N, p.Hdf, p.Wdf, p.Cs, p.Cd);
 }
 
-#ifndef DBN_CFG1_WM
-#define DBN_CFG1_WM 1  // the 128 x 128 tile of the 16-bit storage types as 1 x 4 waves of 128 x 32: no two waves load the same weight fragments from L2 (the
-                       // register-fed B side of the generic loop; 2 = the 2 x 2 layout of rounds 3-5).  configs[4] 10.77 -> 10.64 ms, bf16 step 1753 / 1765 -> 1768
-#endif
 // the four tile configurations of one (NS, AT) family
 template <int NS, int AT>
 int launch_igemm_cfg(IgemmParams& p, int cfg, int mode, hipStream_t st) {
@@ -2094,7 +2044,9 @@ int launch_igemm_cfg(IgemmParams& p, int cfg, int mode, hipStream_t st) {
     }
     switch (cfg) {
         case 1:
-            if constexpr (NS == 1 && (AT == 1 || AT == 2) && DBN_CFG1_WM == 1) return launch_igemm_ns<128, 128, 1, 4, NS, AT>(p, mode, st);
+            // 16-bit storage types: 1 x 4 waves of 128 x 32, no two waves load the same weight fragments from L2 (the register-fed B side of
+            // the generic loop); the 2 x 2 layout of rounds 3-5 measured slower, DESIGN 30
+            if constexpr (NS == 1 && (AT == 1 || AT == 2)) return launch_igemm_ns<128, 128, 1, 4, NS, AT>(p, mode, st);
             else return launch_igemm_ns<128, 128, 2, 2, NS, AT>(p, mode, st);
         case 2: return launch_igemm_ns<256, 64, 4, 1, NS, AT>(p, mode, st);
         case 3: return launch_igemm_ns<128, 64, 2, 2, NS, AT>(p, mode, st);

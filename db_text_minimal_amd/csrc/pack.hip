@@ -123,13 +123,10 @@ struct PackJob {
     int O, I, R, S, mode, Cs, Cd, f;
 };
 
-#ifndef DBN_PACK_GRID
 // workgroups per job (grid-stride inside; those past a job's size leave at once).  48 until late in round 5: the model's largest jobs
 // (512 x 512 x 9) then walked 24 groups of scattered loads per thread, the launch took 256 us in bf16 — on the second stream, but beside the
-// input conversion and the stem, which it slowed (the conversion alone: 29 us, in the step: 107).  bf16 step, one box, interleaved three times:
-// 48: 1731 / 1736 / 1735 images/s, 192: 1742 / 1745 / 1749, 512: 1754 / 1756 / 1755, 1024: 1755 / 1755 / 1757 (12: 1695); fp32 unchanged
-#define DBN_PACK_GRID 512
-#endif
+// input conversion and the stem, which it slowed (the conversion alone: 29 us, in the step: 107); grids of 12 ... 1024 measured: DESIGN 30
+constexpr int PACK_GRID = 512;
 template <int BF16>
 __global__ void pack_many_kernel(const PackJob* __restrict__ jobs, int NS) {
     const PackJob j = jobs[blockIdx.y];
@@ -281,13 +278,10 @@ long dbn_igemm_panel_floats_t(int kind, int O, int I, int R, int S, int mode, in
 }
 
 // Workgroups per parity class of a stride-4 / -8 transposed conv's panels (the pyramid conv's derived panels: 16 / 64 classes of <= 65 536
-// elements, packed every step beside layer1 or — fp32 — in front of the pyramid conv).  FEWER is better here, measured late in round 5 on one
-// box, interleaved three times: 1024: bf16 1645-1651 images/s / fp32 715-716, 256: 1645-1648 / 717-718, 64 (until then): 1678-1684 / 724,
-// 32: 1687-1691 / 726, 16: 1689-1690 / 725.  (The cap of the other panels — the stem's, levels 0 and 1 — goes the other way: 64 or 16
-// instead of 1024 costs fp32 727 -> 717 / 716; those launches sit on the main stream's chain.)
-#ifndef DBN_PACKF_CAP
-#define DBN_PACKF_CAP 16
-#endif
+// elements, packed every step beside layer1 or — fp32 — in front of the pyramid conv).  FEWER is better here (caps of 16 ... 1024 measured late
+// in round 5: DESIGN 30).  The cap of the other panels — the stem's, levels 0 and 1 — goes the other way: 64 or 16
+// instead of 1024 costs fp32 727 -> 717 / 716; those launches sit on the main stream's chain.
+constexpr int PACKF_CAP = 16;
 static int pack_run(const float* w_oihw, int O, int I, int R, int S, int mode, int stride, int ns, float* out, void* stream, int cs = 0,
                     int f16 = 0) {
     DBN_REQUIRE(w_oihw && out && O > 0 && I > 0 && R > 0 && S > 0 && (mode == 0 || mode == 1));
@@ -301,7 +295,7 @@ static int pack_run(const float* w_oihw, int O, int I, int R, int S, int mode, i
     // panel offsets as in igemm_run)
     const int f = (mode == 1 && stride > 1) ? stride : 1;
     const long total = (long)(((dbn_ceil_div(R, f) * dbn_ceil_div(S, f) * Cs + 15) / 16) * 16) * Cd;  // largest class
-    const dim3 grid(dbn_grid(total, 256, f > 2 ? DBN_PACKF_CAP : 1024), f * f);
+    const dim3 grid(dbn_grid(total, 256, f > 2 ? PACKF_CAP : 1024), f * f);
     if (ns == 0)
         hipLaunchKernelGGL(pack_weights_kernel, grid, dim3(256), 0, st, w_oihw, O, I, R, S, mode, Cs, Cd, f, out);
     else
@@ -320,7 +314,7 @@ int dbn_pack_weights_t(int kind, const float* w_oihw, int O, int I, int R, int S
 // up to 4 : O, Cd = mode 0 ? O : I, f = (mode 1 and stride > 1) ? stride : 1).  ns = 0: fp32 panels, 1 / 3: split-bf16.
 int dbn_pack_weights_batched(const void* jobs, int n, int ns, void* stream) {  // ns: panel kind (0 fp32, 1 bf16, 3 bf16x3, 2 fp16)
     DBN_REQUIRE(jobs && n > 0 && (ns == 0 || ns == 1 || ns == 2 || ns == 3));
-    const dim3 grid(DBN_PACK_GRID, n);
+    const dim3 grid(PACK_GRID, n);
     if (ns == 0)
         hipLaunchKernelGGL(pack_many_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const PackJob*>(jobs), 0);
     else if (ns == 2)

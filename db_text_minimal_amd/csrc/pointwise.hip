@@ -386,7 +386,8 @@ __global__ void bnrelu_maxpool_bwd_kernel(const void* __restrict__ y, const floa
                                           const void* __restrict__ pooled, const void* __restrict__ dpool,
                                           void* __restrict__ dz, int N, int H, int W, int C, int Ho, int Wo,
                                           const float* __restrict__ mean, const float* __restrict__ rstd, float* __restrict__ bn_part) {
-    // One thread: QW channel quads (QW = 2: 16-bit storage, eight channels = one 16-byte access; round 5) of a 2x2 block of input pixels
+    // One thread: QW channel quads (QW = 2: 16-bit storage, eight channels = one 16-byte access; round 5: measured slower than QW = 1 — the
+    // 2 x 2 x 2 window arrays double — and no longer instantiated) of a 2x2 block of input pixels
     // (rows 2a, 2a+1, columns 2b, 2b+1).  The four pixels lie in the windows (a..a+1) x (b..b+1) only, so 4 loads of the pooled maxima
     // and 4 of their gradients serve all four (a thread per pixel read 9 + 9: FETCH_SIZE 1.43x the tensors).
     static_assert(QW == 1 || (QW == 2 && AT != 0), "two quads per access: 16-bit storage");
@@ -593,9 +594,6 @@ __global__ __launch_bounds__(256) void bnrelu_maxpool_fwd_arg_kernel(const void*
     }
 }
 
-#ifndef DBN_POOL_STATS_UNROLL
-#define DBN_POOL_STATS_UNROLL 1  // (fp32 729.1 -> 732.2 images/s over three interleaved pairs, bf16 unchanged; same summation order)
-#endif
 // part[2 * C][gridDim.x]: per-block sums of g and g * xhat over the POOLED elements (g = dpool where the code is not 15); threads t, t + C/4, ...
 // of a block hold the same channel quad (256 % (C/4) == 0, host side)
 template <int AT>
@@ -616,8 +614,8 @@ __global__ __launch_bounds__(256) void maxpool_bn_stats_kernel(const void* __res
         s2 += g * ((yp - mu) * rs);
     };
     long i = i0;
-#if DBN_POOL_STATS_UNROLL
     // four items (twelve loads) in flight per thread: beside the last weight-gradient kernel of the step this pass gets few wave slots
+    // (same summation order as one item at a time)
     for (; i + 3 * stride < total; i += 4 * stride) {
         f32x4 dp[4], yp[4];
         unsigned code[4];
@@ -630,7 +628,6 @@ __global__ __launch_bounds__(256) void maxpool_bn_stats_kernel(const void* __res
 #pragma unroll
         for (int k = 0; k < 4; ++k) add(dp[k], yp[k], code[k]);
     }
-#endif
     for (; i < total; i += stride) add(dbn_ld4<AT>(dpool, i), dbn_ld4<AT>(ypool, i), idx[i]);
     __shared__ f32x4 red[2][256];
     red[0][threadIdx.x] = s1;
@@ -1155,15 +1152,12 @@ int dbn_bn_backward_t(int at, const float* sums, int sums_parts, const void* y, 
                                grad_scale);
         }
         // the reduce partials at the front of ws have been consumed by the finalize kernel: the bias partials [C][grid] reuse them
-#ifndef DBN_DBG_SKIP_BN_BWD_APPLY
-#define DBN_DBG_SKIP_BN_BWD_APPLY 0  // 1 (timing-only A/B build, wrong results): the apply pass is not launched — the upper bound of what fusing it into its consumers could save
-#endif
         if constexpr (AT != 0) {
-            if (wide && !DBN_DBG_SKIP_BN_BWD_APPLY)
+            if (wide)
                 hipLaunchKernelGGL((bn_bwd_apply_kernel<AT, 2>), dim3(grid), dim3(256), 0, st, y, zmask, mask_scale, mask_shift, dout, save_mean,
                                    save_rstd, gamma, c1, c2, dy, gout, gout_accumulate, total4, C, dbias_conv ? ws : nullptr);
         }
-        if (!wide && !DBN_DBG_SKIP_BN_BWD_APPLY)
+        if (!wide)
             hipLaunchKernelGGL((bn_bwd_apply_kernel<AT, 1>), dim3(grid), dim3(256), 0, st, y, zmask, mask_scale, mask_shift, dout, save_mean,
                                save_rstd, gamma, c1, c2, dy, gout, gout_accumulate, total4, C, dbias_conv ? ws : nullptr);
     });
@@ -1241,21 +1235,7 @@ int dbn_bnrelu_maxpool_bwd_t(int at, const void* y, const float* scale, const fl
     DBN_REQUIRE((bn_part == nullptr) == (bn_mean == nullptr) && (bn_part == nullptr) == (bn_rstd == nullptr));
     DBN_REQUIRE(!bn_part || 256 % (C / 4) == 0);
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    // (the grid — and with it the number of partial rows the caller sized bn_part for, dbn_maxpool_bwd_parts — is the same for both forms;
-    // the 16-byte form just walks half as many items)
-#ifndef DBN_POOL_BWD_QW2
-#define DBN_POOL_BWD_QW2 0  // the 16-byte form of the BACKWARD measured slower (its 2 x 2 x 2 window arrays double: bf16 step 1663 / 1671 / 1662 / 1665 images/s with the four-channel form, 1636 / 1632 / 1639 / 1631 with this one, interleaved on one box): off
-#endif
-    if (DBN_POOL_BWD_QW2 && (at == 1 || at == 2) && C % 8 == 0) {
-        const dim3 grid(dbn_maxpool_bwd_parts(N, H, W, C));
-        if (at == 1)
-            hipLaunchKernelGGL((bnrelu_maxpool_bwd_kernel<1, 2>), grid, dim3(256), 0, (hipStream_t)stream, y, scale, shift, pooled, dpool, dz, N, H, W,
-                               C, Ho, Wo, bn_mean, bn_rstd, bn_part);
-        else
-            hipLaunchKernelGGL((bnrelu_maxpool_bwd_kernel<2, 2>), grid, dim3(256), 0, (hipStream_t)stream, y, scale, shift, pooled, dpool, dz, N, H, W,
-                               C, Ho, Wo, bn_mean, bn_rstd, bn_part);
-        return dbn_status();
-    }
+    // (the grid is the number of partial rows the caller sized bn_part for: dbn_maxpool_bwd_parts)
     DBN_DISPATCH_AT(at, hipLaunchKernelGGL((bnrelu_maxpool_bwd_kernel<AT, 1>), dim3(dbn_maxpool_bwd_parts(N, H, W, C)), dim3(256), 0,
                                            (hipStream_t)stream, y, scale, shift, pooled, dpool, dz, N, H, W, C, Ho, Wo, bn_mean, bn_rstd,
                                            bn_part));
@@ -1285,9 +1265,6 @@ int dbn_bnrelu_maxpool_fwd_arg_t(int at, const void* y, const float* scale, cons
                                            (hipStream_t)stream, y, scale, shift, out, ix, ypool, N, H, W, C, Ho, Wo));
     return dbn_status();
 }
-#ifndef DBN_POOL_APPLY_QW2
-#define DBN_POOL_APPLY_QW2 1  // 16-bit storage: the apply pass with 16-byte accesses (A/B switch)
-#endif
 static int maxpool_bn_parts(int N, int Ho, int Wo, int C) { return dbn_grid((long)N * Ho * Wo * (C / 4), 256, 2048); }
 // floats of scratch dbn_maxpool_bn_backward_t needs
 long dbn_maxpool_bn_backward_ws_floats(int N, int H, int W, int C) {
@@ -1319,7 +1296,7 @@ int dbn_maxpool_bn_backward_t(int at, const void* y, const void* dpool, const vo
             hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(dbn_ceil_div(C, 8)), dim3(256), 0, st, part, parts, M, C, dgamma, dbeta, c1, c2, grad_scale);
         bool wide = false;
         if constexpr (AT != 0) {
-            if (DBN_POOL_APPLY_QW2 && C % 8 == 0) {
+            if (C % 8 == 0) {  // 16-bit storage: the apply pass with 16-byte accesses
                 wide = true;
                 const dim3 wgrid(dbn_grid((long)N * ((H + 1) / 2) * ((W + 1) / 2) * (C / 8)));
                 hipLaunchKernelGGL((maxpool_bn_bwd_apply_kernel<AT, 2>), wgrid, dim3(256), 0, st, y, dpool, ix, save_mean, save_rstd, gamma, c1, c2, dy, N,

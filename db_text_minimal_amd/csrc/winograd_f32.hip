@@ -19,24 +19,6 @@
 #include <algorithm>
 #include <mutex>
 #include <unordered_map>
-#ifndef DBN_WINO_BATCH
-#define DBN_WINO_BATCH 0  // 1: each point's vector instructions fenced into one batch in front of its MFMAs (measured: 64->64 189 -> 191 us, 256->64 575 -> 593, the LIN form 173 -> 193 with two spills: the LDS latency in front of the batch is then exposed)
-#endif
-#ifndef DBN_WINO_EXP
-#define DBN_WINO_EXP 0
-#endif
-#ifndef DBN_WINO_PAIR12
-#define DBN_WINO_PAIR12 0  // (measured neutral: 64->64 176.7 vs 176.0 us, 256->64 549 vs 550, step 728.7 / 729.0 vs 728.3 / 727.2 images/s interleaved: off) round 5: points 1 and 2 (both V_1 = r_1 + r_2 and V_2 = r_2 - r_1 come from the same two row combinations) as ONE phase: 32 MFMAs over FOUR accumulator chains instead of twice 16 over two (profiles/r03_mfma_peak_probe.txt: 0.93 -> 0.99 of the pipe)
-#endif
-#ifndef DBN_WINO_ROWCOMB
-#define DBN_WINO_ROWCOMB 1  // round 5: V through the shared row combinations r_c = d[a1][c] + sa * d[a2][c], formed lazily (see below)
-#endif
-// timing experiments (wrong results by construction; tools/winograd_probe.py with DBN_LIB_PATH): 1 weight fragments of the first channel
-// block only, 2 no LDS reads / transform arithmetic in the loop, 3 no exchange / statistics in the epilogue, 5 no patch store / barrier
-// in the loop, 6 = 3 + 5, 7 = 2 + 3 + 5 (what is left: prologue, MFMAs, weight loads, plain stores), 8 = 7 + 1 (... without the weight loads)
-#define DBN_WX_NOXFORM (DBN_WINO_EXP == 2 || DBN_WINO_EXP == 7 || DBN_WINO_EXP == 8)
-#define DBN_WX_NOEXCH (DBN_WINO_EXP == 3 || DBN_WINO_EXP == 6 || DBN_WINO_EXP == 7 || DBN_WINO_EXP == 8)
-#define DBN_WX_NOBAR (DBN_WINO_EXP == 5 || DBN_WINO_EXP == 6 || DBN_WINO_EXP == 7 || DBN_WINO_EXP == 8)
 
 namespace {
 
@@ -60,10 +42,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     constexpr int P_STAGE = CBS * P_PATCH;  // one stage = the patches of CBS consecutive channel blocks; two stages
     static_assert(2 * P_STAGE <= X_FLOATS / 4, "the patch buffers live inside the exchange region");
     // + the statistics / sums scratch [<= 3][4][64] floats, a flag, 8 counts | the apply-on-load coefficients of <= 512 channels | the next item
-#ifndef DBN_WINO_LDSPAD
-#define DBN_WINO_LDSPAD 0  // (timing experiment: extra LDS in 16-byte units — 1024 pushes a workgroup over half a CU's LDS: one resident workgroup per CU)
-#endif
-    __shared__ f32x4 smem[X_FLOATS / 4 + (3 * 4 * 64) / 4 + 4 + 2 * 128 + 1 + DBN_WINO_LDSPAD];
+    __shared__ f32x4 smem[X_FLOATS / 4 + (3 * 4 * 64) / 4 + 4 + 2 * 128 + 1];
     const int tid = threadIdx.x;
     // ---- PERSISTENT workgroups (round 5): the grid is at most two workgroups per CU; each pulls (patch, 64-channel tile) items from
     // per-XCD counters until none is left (dbn_xcd_remap's layout: XCD x owns a contiguous run of items, so the halo rows of neighbouring
@@ -239,9 +218,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             constexpr int st_ = decltype(SET)::value;
             const int g = min(w_next, w_last);
             ++w_next;
-#if DBN_WINO_EXP == 1 || DBN_WINO_EXP == 8  // (timing experiment, wrong results: the weight fragments of the first channel block only — no L2 weight traffic; 8 = 7 + this)
-            if (w_next > 4) return;
-#endif
             const unsigned so = (unsigned)((g >> 2) * 16 + 4 * wave + (g & 3)) * point_bytes;
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2)
@@ -286,8 +262,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         load_patch(0, 0);
         issue_w(std::integral_constant<int, 0>{});
         issue_w(std::integral_constant<int, 1>{});
-        if constexpr (DBN_WINO_ROWCOMB && DBN_WINO_PAIR12 && !(DBN_WINO_EXP == 2 || DBN_WINO_EXP == 7 || DBN_WINO_EXP == 8) && !LIN)
-            issue_w(std::integral_constant<int, 2>{});  // (paired order: points 1 and 2 start together)
         store_patch(0, 0, 0);
         if constexpr (CBS == 2) {
             load_patch(0, 1);
@@ -297,18 +271,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         DBN_TRACE_MARK(1);
-#ifndef DBN_WINO_PRIO
-#define DBN_WINO_PRIO 0  // wave priority experiment: 1 = the main loop above the set-up / epilogue phases of the co-resident workgroup, 2 = below
-#endif
-        if (DBN_WINO_PRIO == 1) __builtin_amdgcn_s_setprio(3);
-        if (DBN_WINO_PRIO == 2) __builtin_amdgcn_s_setprio(0);
         const int nst = ncb / CBS;  // stages (CBS == 2: the launcher checked that ncb is even)
         for (int st = 0; st < nst; ++st) {
             load_patch(st + 1, 0);  // (past the last block: out-of-range offsets, zeros, never stored)
 #pragma unroll
             for (int u = 0; u < CBS; ++u) {
             const int cb = st * CBS + u;
-            if (CBS == 2 && u == 1 && !DBN_WX_NOBAR) {
+            if (CBS == 2 && u == 1) {
                 // the next stage's FIRST block goes to LDS already (its buffer was last read in stage st - 1, and every wave has passed the
                 // barrier that ended it), and the second block's fetch takes over the registers
                 if (st + 1 < nst) store_patch((st + 1) & 1, st + 1, 0);
@@ -320,8 +289,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             // + 44 vector instructions per block instead of 32 + 96 — 3-8 % SLOWER: one long vector phase per block overlaps the other
             // resident wave's MFMAs worse than four short ones; issuing the next point's LDS reads ahead of the current point's MFMAs:
             // neutral, and its 32 registers are better spent on the weight fragments' prefetch distance.)
-            constexpr bool RC = DBN_WINO_ROWCOMB && !DBN_WX_NOXFORM && !LIN;  // (the LIN form has no registers for it: 51 spilled dwords)
-            constexpr bool PAIRED = RC && DBN_WINO_PAIR12;
+            constexpr bool RC = !LIN;  // round 5: V through the shared row combinations, formed lazily (the LIN form has no registers for it: 51 spilled dwords)
             // The wave's four points (i, 0..3) take the SAME two patch rows (a1, a2) and differ in the column pair only: with
             //   r_c = d[a1][c] + sa * d[a2][c]   (c = 0..3),   V_0 = r_0 - r_2,  V_1 = r_1 + r_2,  V_2 = r_2 - r_1,  V_3 = r_1 - r_3
             // a channel block needs 16 LDS reads and 64 vector instructions instead of 32 and 96.  Round 4 had tried this with all four V formed
@@ -342,24 +310,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             auto point = [&](auto J, auto FIRST) {
                 constexpr int j = decltype(J)::value;
                 constexpr bool first = decltype(FIRST)::value;  // channel block 0: the accumulators start here
-                if constexpr (!PAIRED) {
-                    issue_w(std::integral_constant<int, (j + 2) & 3>{});  // the weight fragments of the point after the next (set = point index)
-                } else if constexpr (j == 3) {  // (paired order, see pair12: sets 1 and 2 of the NEXT block, two phases ahead of its pair)
-                    issue_w(std::integral_constant<int, 1>{});
-                    issue_w(std::integral_constant<int, 2>{});
-                }
+                issue_w(std::integral_constant<int, (j + 2) & 3>{});  // the weight fragments of the point after the next (set = point index)
                 __builtin_amdgcn_sched_barrier(0);
                 // B^T column j: 0: d0 - d2;  1: d1 + d2;  2: d2 - d1;  3: d1 - d3
                 constexpr int b1 = j == 0 ? 0 : (j == 2 ? 2 : 1), b2 = j == 0 ? 2 : (j == 1 ? 2 : (j == 2 ? 1 : 3));
                 constexpr bool plus = j == 1;
                 f32x4 v[2];
-#if DBN_WX_NOXFORM  // (timing experiment, wrong results: no LDS reads / transform arithmetic in the loop)
-                // (round 5: NOT the patch registers — `pr` is rewritten by load_patch at the top of every channel block, so MFMAs fed from it
-                // waited a global-load latency per block and builds 2 / 7 / 8 measured that wait, not the skeleton.  An opaque per-lane value.)
-                v[0] = f32x4{(float)lane, 1.f, 2.f, 3.f};
-                v[1] = f32x4{4.f, (float)li, 6.f, 7.f};
-                asm volatile("" : "+v"(v[0]), "+v"(v[1]));
-#else
                 if constexpr (RC) {
                     if constexpr (j == 0) {
                         form_r(std::integral_constant<int, 0>{});
@@ -381,12 +337,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         for (int e = 0; e < 4; ++e) v[s2][e] = fmaf(sa, t2[e], t1[e]);  // (sa = +-1: exact)
                     }
                 }
-#endif
-                // (DBN_WINO_BATCH: the point's 24 vector instructions fenced into ONE batch in front of its 16 MFMAs — a vector instruction
-                // between two MFMAs costs ~13 clocks of the fp32 matrix pipe, in a batch ~5 — measured slower here, see the define)
-#if DBN_WINO_BATCH
-                __builtin_amdgcn_sched_barrier(0);
-#endif
+                // (the point's vector instructions are NOT fenced into one batch in front of its MFMAs: measured slower, and points 1 and 2 as
+                // one 32-MFMA phase measured neutral: DESIGN 30)
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
@@ -397,46 +349,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                             const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                             acc[j][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[s2][e], rw[j][s2][b][e], (first && s2 == 0 && e == 0) ? zero16 : acc[j][b], 0, 0, 0);
                         }
-#if DBN_WINO_BATCH
-                __builtin_amdgcn_sched_barrier(0);
-#endif
             };
-            auto pair12 = [&](auto FIRST) {
-                constexpr bool first = decltype(FIRST)::value;
-                // weight prefetch in the paired order (every set at least two point-times ahead of its use, none rewritten while in use):
-                // here point 3 of this block and point 0 of the next; point 3 then fetches sets 1 and 2 of the next block; the prologue 0, 1, 2
-                issue_w(std::integral_constant<int, 3>{});
-                issue_w(std::integral_constant<int, 0>{});
-                __builtin_amdgcn_sched_barrier(0);
-                form_r(std::integral_constant<int, 1>{});
-                f32x4 v1[2], v2[2];
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    v1[s2] = rc[RC ? 1 : 0][s2] + rc[RC ? 2 : 0][s2];
-                    v2[s2] = rc[RC ? 2 : 0][s2] - rc[RC ? 1 : 0][s2];
-                }
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-#pragma unroll
-                        for (int b = 0; b < 2; ++b) {
-                            const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                            acc[1][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(v1[s2][e], rw[1][s2][b][e], (first && s2 == 0 && e == 0) ? zero16 : acc[1][b], 0, 0, 0);
-                            acc[2][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(v2[s2][e], rw[2][s2][b][e], (first && s2 == 0 && e == 0) ? zero16 : acc[2][b], 0, 0, 0);
-                        }
-            };
-            if constexpr (PAIRED) {
-                if (cb == 0) {
-                    point(std::integral_constant<int, 0>{}, std::true_type{});
-                    pair12(std::true_type{});
-                    point(std::integral_constant<int, 3>{}, std::true_type{});
-                } else {
-                    point(std::integral_constant<int, 0>{}, std::false_type{});
-                    pair12(std::false_type{});
-                    point(std::integral_constant<int, 3>{}, std::false_type{});
-                }
-            } else if (!LIN && cb == 0) {
+            if (!LIN && cb == 0) {
                 point(std::integral_constant<int, 0>{}, std::true_type{});
                 point(std::integral_constant<int, 1>{}, std::true_type{});
                 point(std::integral_constant<int, 2>{}, std::true_type{});
@@ -448,7 +362,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 point(std::integral_constant<int, 3>{}, std::false_type{});
             }
             }  // (u)
-            if (st + 1 < nst && !DBN_WX_NOBAR) {
+            if (st + 1 < nst) {
                 // the other buffer was last read in block cb - 1, and every wave has passed the barrier that ended it
 #if DBN_TRACE
                 tr_t = __builtin_amdgcn_s_memrealtime();
@@ -463,8 +377,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
         }
         DBN_TRACE_MARK(2);
-        if (DBN_WINO_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-        if (DBN_WINO_PRIO == 2) __builtin_amdgcn_s_setprio(3);
 #if DBN_TRACE
         if (p.trace && threadIdx.x == 0) p.trace[(long)blockIdx.x * 8 + 5] = tr_bar;  // ticks spent from "MFMAs issued" to "past the barrier"
 #endif
@@ -474,20 +386,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         int next_idx = 0;
         if (PERSIST && p.work && tid == 0) next_idx = pull();
 
-#if DBN_WX_NOEXCH  // (timing experiment, wrong results: no exchange, no statistics — what would an epilogue that stays in registers cost?)
-        {
-            const unsigned pitch_ = (unsigned)p.Cd * 4u;
-            const __amdgpu_buffer_rsrc_t rsrcD_ = __builtin_amdgcn_make_buffer_rsrc(p.dst, 0, (unsigned)((long)p.N * p.Hdf * p.Wdf * p.Cd * 4), 0x00020000);
-            const unsigned base_ = (unsigned)((pn * p.Hdf + ph0 + (wave >> 1)) * p.Wdf + pw0 + (wave & 1) + 8 * lh) * pitch_ + (unsigned)(n0 + li) * 4u;
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    const float v_ = ((acc[0][b][r] + acc[1][b][r]) + acc[2][b][r]) - acc[3][b][r];
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v_), rsrcD_, (int)(base_ + (unsigned)(2 * (r >> 2) * p.Wdf + 2 * (r & 3)) * pitch_) + b * 128, 0, 0);
-                }
-        }
-#else
         // ---- output transform.  Along j (this wave holds M_i0 .. M_i3): T_i[dx] = A^T row dx: dx 0: M0 + M1 + M2;  dx 1: M1 - M2 - M3
         // Exchange layout: [(i*2 + dx)*2 + b][lane][4 groups of four rows], 16-byte accesses; the group index is XOR-swizzled with bits 1-2
         // of the lane so that the eight lanes of one LDS cycle (64 bytes apart) hit eight different 16-byte bank groups.  (First form:
@@ -811,7 +709,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int b = 0; b < 2; ++b) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y[b][r]), rsrcD, (int)off + b * 128, 0, 0);
         }
-#endif
         DBN_TRACE_MARK(3);
         // optional in-kernel finalize of the statistics rows (IgemmParams::bnf_cnt, igemm_common.h), behind this item's output stores
         if (p.stats && p.bnf_cnt) {
@@ -879,12 +776,10 @@ struct WinoPackJob {
     float* out;
     int O, I, Cs, dgrad;
 };
-#ifndef DBN_WPACK_GRID
 // workgroups per job: FEW on purpose — the launch runs on the second stream beside the fp32 stem conv and ends long before the first
-// Winograd conv needs a panel; wider grids finish sooner and slow the stem more (fp32 step, one box, interleaved three times: 16: 727 / 724 /
-// 724 images/s, 64: 723 / 720 / 721, 256: 720 / 720 / 720) — the opposite of pack_many_kernel in the 16-bit modes (pack.hip)
-#define DBN_WPACK_GRID 16
-#endif
+// Winograd conv needs a panel; wider grids finish sooner and slow the stem more — the opposite
+// of pack_many_kernel in the 16-bit modes (pack.hip)
+constexpr int WPACK_GRID = 16;
 __global__ void winograd_pack_many_kernel(const WinoPackJob* __restrict__ jobs) {
     const WinoPackJob j = jobs[blockIdx.y];
     const long total = (long)j.Cs * j.O;
@@ -917,7 +812,7 @@ __global__ void winograd_pack_many_kernel(const WinoPackJob* __restrict__ jobs) 
 }  // namespace
 
 int dbn_launch_winograd_pack_many(const void* jobs, int n, hipStream_t st) {
-    hipLaunchKernelGGL(winograd_pack_many_kernel, dim3(DBN_WPACK_GRID, n), dim3(256), 0, st, reinterpret_cast<const WinoPackJob*>(jobs));
+    hipLaunchKernelGGL(winograd_pack_many_kernel, dim3(WPACK_GRID, n), dim3(256), 0, st, reinterpret_cast<const WinoPackJob*>(jobs));
     return dbn_status();
 }
 

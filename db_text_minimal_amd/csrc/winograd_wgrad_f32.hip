@@ -15,12 +15,6 @@
 // reduction kernel adds the slabs in fp64 in a fixed order and applies G^T . G (deterministic, no atomics).
 #include "igemm_common.h"
 #include <algorithm>
-#ifndef DBN_WWG_PIPE
-#define DBN_WWG_PIPE 1  // 0: the k-steps in the compiler's order (A/B builds)
-#endif
-#ifndef DBN_WWG_EXP
-#define DBN_WWG_EXP 0  // timing experiments (wrong results): 1 = the first patch only (no staging / barriers in the loop), 2 = no LDS reads / transforms
-#endif
 
 namespace {
 
@@ -240,17 +234,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             // patch g + 1 (in registers since the previous iteration) goes to the OTHER image — every wave left it at the barrier that
             // ended iteration g - 1 — and patch g + 2 starts its way from memory; both overlap this patch's matrix phase
             cbuf = (g - g0) & 1;
-            if (DBN_WWG_EXP != 1) {
-                if (g + 1 < g1) store_group();
-                if (g + 2 < g1) load_group(g + 2);
-            }
+            if (g + 1 < g1) store_group();
+            if (g + 2 < g1) load_group(g + 2);
         }
         const int xoff2 = cbuf * (XCH + YCH) * 2, yoff4 = cbuf * (XCH + YCH) * 4;  // offsets of the image in float2 / float units
-#if DBN_WWG_PIPE
         if constexpr (!LIN) {
             // k-steps in a two-stage software pipeline: the LDS reads of step s + 1 go out BEFORE the eight MFMAs of step s, its operands
             // are formed AFTER they are issued (while they run) — the compiler's order is reads -> wait -> ~40 vector instructions ->
-            // 8 MFMAs per step, a latency chain the second resident wave of the SIMD only partly covers (-DDBN_WWG_EXP=5/6).
+            // 8 MFMAs per step, a latency chain the second resident wave of the SIMD only partly covers (the compiler's order for this
+            // form measured slower: DESIGN 30).
             f32x2 U1[4], U2[4], V[4];
             float dd[4], D[4];
             auto fetch = [&](int s_) {
@@ -303,63 +295,37 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 __builtin_amdgcn_sched_barrier(0);
                 if (s + 1 < 16) form();
             }
-        } else
-#endif
+        } else {
+            // (the LIN form: the k-steps in the compiler's order)
 #pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            int xo, yo;
-            float c0s = c0, c1s = c1;
-            if constexpr (LIN) {
+            for (int s = 0; s < 16; ++s) {
                 const int t = t0 + 2 * s + lh;
                 const bool ok = t < TI;
                 int ty, tx;
                 divmod24(ok ? t : t0, TW, rTW, ty, tx);
                 ty -= tr0;
-                xo = (2 * ty * prow + 2 * tx) * 32;
-                yo = (2 * ty * yrow + 2 * tx) * 64;
-                c0s = ok ? c0 : 0.f;
-                c1s = ok ? c1 : 0.f;
-            } else {
-                xo = (2 * (s >> 2) * WG_XROW + 4 * (s & 3)) * 32;
-                yo = (2 * (s >> 2) * WG_YROW + 4 * (s & 3)) * 64;
+                const int xo = (2 * ty * prow + 2 * tx) * 32, yo = (2 * ty * yrow + 2 * tx) * 64;
+                const float c0s = ok ? c0 : 0.f, c1s = ok ? c1 : 0.f;
+                f32x2 R[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const f32x2 u1 = Xr1[xoff2 + xo + q * 32], u2 = Xr2[xoff2 + xo + q * 32];
+                    R[q][0] = fmaf(sa, u2[0], u1[0]);  // (sa = +-1: exact)
+                    R[q][1] = fmaf(sa, u2[1], u1[1]);
+                }
+                const float* const Yc = Yb + yoff4;
+                const float d00 = Yc[yo], d01 = Yc[yo + 64], d10 = Yc[yo + yrow * 64], d11 = Yc[yo + yrow * 64 + 64];
+                const f32x2 V[4] = {R[0] - R[2], R[1] + R[2], R[2] - R[1], R[1] - R[3]};
+                const float r0 = fmaf(c1s, d10, c0s * d00), r1 = fmaf(c1s, d11, c0s * d01);
+                const float D[4] = {r0, r0 + r1, r0 - r1, -r1};
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) acc[j][h] = __builtin_amdgcn_mfma_f32_32x32x2f32(D[j], V[j][h], acc[j][h], 0, 0, 0);
             }
-            f32x2 R[4];
-#if DBN_WWG_EXP == 2 || DBN_WWG_EXP == 6  // (6: the vector instructions on register operands, no LDS reads)
-            for (int q = 0; q < 4; ++q) { R[q][0] = rx[q][0]; R[q][1] = rx[q][1]; }
-            const float d00 = rx[0][0], d01 = rx[0][1], d10 = rx[1][0], d11 = rx[1][1];
-#if DBN_WWG_EXP == 6
-            for (int q = 0; q < 4; ++q) { R[q][0] = fmaf(sa, rx[q][1], R[q][0]); R[q][1] = fmaf(sa, rx[q][2], R[q][1]); }
-#endif
-#else
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f32x2 u1 = Xr1[xoff2 + xo + q * 32], u2 = Xr2[xoff2 + xo + q * 32];
-#if DBN_WWG_EXP == 5
-                R[q][0] = u1[0];
-                R[q][1] = u2[1];
-#else
-                R[q][0] = fmaf(sa, u2[0], u1[0]);  // (sa = +-1: exact)
-                R[q][1] = fmaf(sa, u2[1], u1[1]);
-#endif
-            }
-            const float* const Yc = Yb + yoff4;
-            const float d00 = Yc[yo], d01 = Yc[yo + 64], d10 = Yc[yo + yrow * 64], d11 = Yc[yo + yrow * 64 + 64];
-#endif
-#if DBN_WWG_EXP == 2 || DBN_WWG_EXP == 5  // (5: the LDS reads, no transform arithmetic)
-            const f32x2 V[4] = {R[0], R[1], R[2], R[3]};
-            const float D[4] = {d00, d01, d10, d11};
-#else
-            const f32x2 V[4] = {R[0] - R[2], R[1] + R[2], R[2] - R[1], R[1] - R[3]};
-            const float r0 = fmaf(c1s, d10, c0s * d00), r1 = fmaf(c1s, d11, c0s * d01);
-            const float D[4] = {r0, r0 + r1, r0 - r1, -r1};
-#endif
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int h = 0; h < 2; ++h) acc[j][h] = __builtin_amdgcn_mfma_f32_32x32x2f32(D[j], V[j][h], acc[j][h], 0, 0, 0);
         }
         if constexpr (!LIN) {
-            if (g + 1 < g1 && DBN_WWG_EXP != 1) __syncthreads();  // patch g + 1 is in LDS, and every wave has read patch g
+            if (g + 1 < g1) __syncthreads();  // patch g + 1 is in LDS, and every wave has read patch g
         }
     }
     // ---- partial sums -> slab [split][sub][point][o][i]: accumulator row (r & 3) + 8 (r >> 2) + 4 lh = output channel within this wave's

@@ -880,7 +880,7 @@ class Engine:
             self.prof.begin('conv3x3_wres16_kernel<%d,%d,%d,%d>' % (at, geom[3], Cd, mode), flops, nbytes, tag)
             return
         label = IGEMM_TILE_NAMES[cfg & 15] % (mode, self.ns, at, 'true' if cfg & 16 else 'false', epi, blk)
-        if (cfg & 15) == 1 and at in (1, 2) and self.ns == 1:  # round 6: the 128 x 128 tile of the 16-bit storage types runs as 1 x 4 waves (csrc/igemm_kernel.h DBN_CFG1_WM)
+        if (cfg & 15) == 1 and at in (1, 2) and self.ns == 1:  # round 6: the 128 x 128 tile of the 16-bit storage types runs as 1 x 4 waves (csrc/igemm_kernel.h launch_igemm_cfg)
             label = label.replace('<128,128,2,2,', '<128,128,1,4,')
         self.prof.begin(label, flops, nbytes, tag)
 
