@@ -151,18 +151,6 @@ class Engine:
     def __init__(self, model):
         self.model = model
         self.L = _lib.lib()
-        if 'DBN_PATCH_F32' in os.environ:  # A/B runs: 0 exact fp32 on the gather loop everywhere, 1 on the pixel-patch kernel wherever eligible
-            self.L.dbn_set_patch_conv(2 if os.environ['DBN_PATCH_F32'] == '0' else 3)
-        if 'DBN_WINO_PERSISTENT' in os.environ:  # A/B runs: 0 one workgroup per item, 1 persistent workgroups pulling items, 2 static schedule
-            self.L.dbn_set_winograd_persistent(int(os.environ['DBN_WINO_PERSISTENT']))
-        if 'DBN_WINO_CBS' in os.environ:  # A/B runs: channel blocks per barrier of the Winograd patch form (1 | 2)
-            self.L.dbn_set_winograd_blocks_per_barrier(int(os.environ['DBN_WINO_CBS']))
-        if 'DBN_WINO_STAGGER' in os.environ:  # A/B runs: permille of one item's matrix time (0 = off)
-            self.L.dbn_set_winograd_stagger(int(os.environ['DBN_WINO_STAGGER']))
-        if 'DBN_PHASE_PRIO' in os.environ:  # A/B runs
-            self.L.dbn_set_phase_priority(int(os.environ['DBN_PHASE_PRIO']))
-        if 'DBN_STAGGER' in os.environ:  # A/B runs (permille of the nominal first-round stagger of the fp32 convs)
-            self.L.dbn_set_stagger(int(os.environ['DBN_STAGGER']))
         self.bufs = {}
         self.packs = {}
         self.pack_src = {}  # pack key -> parameter tensor, for repack_params()
@@ -184,7 +172,7 @@ class Engine:
         self._bias_done = set()
         self._bnb_sums = {}     # bn name -> (partials [2][C][rows], rows) produced by the data gradient that wrote its dout
         self._reduce_pending = []    # deferred slab reductions of this backward pass: (key, job record)
-        self._wgrad_fifo = []        # weight gradients queued for a late launch (late_wgrad)
+        self._wgrad_fifo = []        # weight gradients queued for a late launch (conv_wgrad)
         self._wino_src = {}          # Winograd panel key -> (parameter, panel, O, I, cs, dgrad)
         self._wino_jobs = None
         self._reduce_job_cache = {}  # (layer, phase-2 arguments) -> dbn_wgrad_reduce_job
@@ -215,7 +203,6 @@ class Engine:
         self.side_priority = None  # HIP stream priority of the side stream (None: default)
         self._side = None
         self._side_used = False
-        self._slab_free = [None, None]  # per slab scratch: event of the reduction that last read it
 
     # ------------------------------------------------------------------ memory
     @property
@@ -360,15 +347,7 @@ class Engine:
         finally:
             self._in_side = False
 
-    def _side_waits_for_reductions(self):
-        """Before a gradient bucket is announced from the side stream its reductions (third stream) must have been ordered in."""
-        if self._side2_used and self._in_side:
-            torch.cuda.current_stream(self.flat.device).wait_stream(self._side2)
-
     def join_side(self):
-        if self._side2_used:  # the reduction stream (see reduce_stream) joins first
-            torch.cuda.current_stream(self.flat.device).wait_stream(self._side2)
-            self._side2_used = False
         if self._side_used:
             torch.cuda.current_stream(self.flat.device).wait_stream(self._side)
             self._side_used = False
@@ -446,7 +425,6 @@ class Engine:
         return self.at, ptr
 
     fuse_bn_bwd_sums = True  # data gradients also reduce the two sums of the BatchNorm backward that consumes their output
-    bnb_finalize_in_kernel = os.environ.get('DBN_BNB_FINAL', '0') == '1'  # ... and fold them to the per-channel results themselves (last-arriver, fixed order).  OFF since round 6 (DBN_BNB_FINAL=1: on): the per-workgroup hand-over costs more than the finalize launches it removes — one box, interleaved: fp32 725.9 / 726.9 -> 729.8 / 730.9 images/s, bf16 1708.7 -> 1780.5 (the same finding as for the statistics rows, bn_final_in_kernel)
 
     def _bnb_eligible(self, args):
         """Can this igemm call (dbn_igemm_f32 argument list) carry the BatchNorm-backward sums of its consumer?"""
@@ -465,7 +443,8 @@ class Engine:
         """args = the dbn_igemm_f32 argument list without the trailing stream.
         consumer: (bn_name, y, zmask) — the BatchNorm whose output gradient this call is the LAST writer of (zmask None: ReLU
         directly on that BatchNorm, mask recomputed from y).  When the call is eligible its epilogue also produces that
-        BatchNorm-backward's two per-channel sums; they wait in self._bnb_sums[bn_name] for bn_backward()."""
+        BatchNorm-backward's two per-channel sums as partial rows (no in-kernel finalize: a null pointer where the BnbFinal record goes);
+        they wait in self._bnb_sums[bn_name] for bn_backward()."""
         N, Hs, Ws, Cs, Hd, Wd, Cd, R, S, stride, pad, mode = args[4:16]
         at, srcp = self._src(args[0], Cs)
         if consumer is not None and self._bnb_eligible(args):
@@ -483,30 +462,12 @@ class Engine:
                 assert zmask is not None and second[1].shape == y.shape
                 y2, mean2, rstd2 = second[1], self.bufs[second[0] + '/mean'], self.bufs[second[0] + '/rstd']
                 part2 = self.fbuf(second[0] + '/bnb_part', 2 * Cd * rows)
-            fin = None
-            if self.bnb_finalize_in_kernel:
-                # the data gradient's last workgroups also fold the partial rows: no finalize launch between it and the apply pass
-                G = self.grad_views
-                cnt = self.bufs.get(bn_name + '/bnb_cnt')
-                ncnt = self.L.dbn_igemm_bn_final_counters(rows, Cd)
-                if cnt is None or cnt.numel() != ncnt or cnt.device != self.flat.device:
-                    cnt = torch.zeros(ncnt, device=self.flat.device, dtype=torch.int32)  # (the kernels leave them zero)
-                    self.bufs[bn_name + '/bnb_cnt'] = cnt
-                grp = self.fbuf(bn_name + '/bnb_grp', self.L.dbn_igemm_bn_final_group_floats(rows, Cd))
-                c1c2 = self.fbuf(bn_name + '/bnb_c1c2', 2 * Cd)
-                fin = _lib.BnbFinal(cnt.data_ptr(), grp.data_ptr(), c1c2.data_ptr(), G[bn_name + '.weight'].data_ptr(),
-                                    G[bn_name + '.bias'].data_ptr(), None, None, None, self.grad_scale)
-                if second is not None:
-                    c1c2b = self.fbuf(second[0] + '/bnb_c1c2', 2 * Cd)
-                    fin.c1c2_2, fin.dgamma_2, fin.dbeta_2 = (c1c2b.data_ptr(), G[second[0] + '.weight'].data_ptr(),
-                                                             G[second[0] + '.bias'].data_ptr())
             check(self.L.dbn_igemm_bnsums_t(at, self.ns, srcp, *args[1:], y.data_ptr(), _p(zmask), _p(msc), _p(msh),
                                             self.bufs[bn_name + '/mean'].data_ptr(), self.bufs[bn_name + '/rstd'].data_ptr(),
-                                            part.data_ptr(), _p(y2), _p(mean2), _p(rstd2), _p(part2),
-                                            ctypes.byref(fin) if fin is not None else None, self.stream), what)
-            self._bnb_sums[bn_name] = (c1c2, -1) if fin is not None else (part, rows)
+                                            part.data_ptr(), _p(y2), _p(mean2), _p(rstd2), _p(part2), None, self.stream), what)
+            self._bnb_sums[bn_name] = (part, rows)
             if second is not None:
-                self._bnb_sums[second[0]] = (c1c2b, -1) if fin is not None else (part2, rows)
+                self._bnb_sums[second[0]] = (part2, rows)
             return
         ks, slab = 1, None
         if self.splitk and (mode == 0 or stride == 1):
@@ -578,11 +539,11 @@ class Engine:
         idle until the first lateral conv, and the main stream joins it again before the pyramid conv), instead of lazily in front of
         their first use on the MAIN stream: there they sat on the critical path, and the data-gradient panels' pack, a small grid, took
         0.44 ms beside the weight-gradient stream (round-4 trace: 0.6 ms of the 22.7 ms step).  (Together with the other panels right
-        after the optimizer step was measured first: 700 -> 692 images/s — the first conv behind the stem then waits for all of it.)"""
+        after the optimizer step was measured first: 700 -> 692 images/s — the first conv behind the stem then waits for all of it.)
+        In the 16-bit storage modes only."""
         src = self._fpn_src
         beside = self.overlap_repack and self.overlap_wgrad
-        on = self.fpn_repack_early == '1' or (self.fpn_repack_early == '' and self.at != 0)
-        if not on or src is None or not beside or self._in_side:
+        if self.at == 0 or src is None or not beside or self._in_side:
             return
         name, conv, Cg = src
         ent = self.packs.get((name, 'combined'))
@@ -601,9 +562,6 @@ class Engine:
         with self.side_stream():
             run()
 
-    # measured on one box, interleaved: exact fp32 702.9-704.7 images/s without vs 698.0-701.9 with (the step there is bound by the two
-    # streams' total work, not by the main stream's chain); bf16 1600 / 1613 without vs 1628 / 1622 with: '' = in the 16-bit modes only
-    fpn_repack_early = os.environ.get('DBN_FPN_REPACK_EARLY', '')
     _fpn_src = None
 
     def _repack_winograd(self, beside):
@@ -626,7 +584,7 @@ class Engine:
     # ------------------------------------------------------------------ kernels
     # 3x3 / stride-1 / pad-1 FORWARD convolutions of the exact-fp32 path through Winograd F(2x2, 3x3) (csrc/winograd_f32.hip): fp32
     # arithmetic, 2.25x fewer matrix FLOPs; the result equals the direct convolution up to fp32 rounding (another summation order).
-    winograd = os.environ.get('DBN_WINOGRAD', '1') == '1'
+    winograd = True  # (off: the direct kernels)
 
     # ---- per-layer plan (round 5, review item 9): WHICH kernel family and fusion form a conv takes at one (geometry, input shape, conv math,
     # mode) is decided in ONE place and cached; the call sites (_winograd_ok, lazy_act, wgrad, _fold_ok, conv_bn_act_eval) read it.  The key
@@ -722,13 +680,9 @@ class Engine:
 
     splitk = True  # split the reduction of convs with few output tiles (dbn_igemm_splitk_plan)
     fuse_bn_stats = True  # accumulate train-mode BN statistics in the conv epilogue (no separate statistics pass)
-    # round 6: ... and fold the per-tile rows in the conv's own last workgroups (dbn_conv_bn_set_final): no bn_finalize_tiles_kernel launch —
-    # 7 us of kernel + ~6 us of dependent-dispatch gap, 32 times a step — between a conv and whatever consumes its BatchNorm's coefficients.
-    # Built, tested (tests/test_bn_final_gpu.py), measured and OFF: 277 -> 245 launches per fp32 step, but 711.4 / 711.9 images/s against
-    # 726.8 / 723.7 with the finalize kernels (one box, interleaved): every workgroup of every conv pays the hand-over (its row stores drained,
-    # an atomic round trip, two barriers: ~2-3 us at the end of a 20-70 us lifetime, six rounds per launch) to save one ~13 us launch.
-    # DBN_BN_FINAL=1 turns it on.
-    bn_final_in_kernel = os.environ.get('DBN_BN_FINAL', '0') == '1'
+    # ... and fold the per-tile rows in the conv's own last workgroups (dbn_conv_bn_set_final) instead of a bn_finalize_tiles_kernel launch.
+    # Off: measured slower; tests/test_bn_final_gpu.py turns it on.
+    bn_final_in_kernel = False
 
     def _announce_bn_final(self, bn_name, rows, C):
         """Counters (zero once: the kernels leave them zero) and group scratch of this BatchNorm's in-kernel statistics finalize."""
@@ -795,11 +749,9 @@ class Engine:
             self.prof.end()
         return y, sc, sh
 
-    # ConvTranspose2d(64 -> 64, 2x2, stride 2) forward in 16-bit storage through its own kernel (round 5, csrc/convt16.hip: the layer is
-    # HBM-bound and the generic parity-class launch ran it at 2.5x its memory time).  DBN_CONVT16=0: the generic launch.
-    stem16_pool = os.environ.get('DBN_STEM16_POOL', '1') == '1'  # inference: the 16-bit stem kernel applies BatchNorm + ReLU and pools (one launch)
-    pw16 = os.environ.get('DBN_PW16', '1') == '1'  # inference: pointwise convs 64 -> 64 | 256 on 16-bit storage through csrc/convt16.hip's kernel
-    convt16 = os.environ.get('DBN_CONVT16', '1') == '1'
+    stem16_pool = True  # inference: the 16-bit stem kernel applies BatchNorm + ReLU and pools (one launch)
+    pw16 = True  # inference: pointwise convs 64 -> 64 | 256 on 16-bit storage through csrc/convt16.hip's kernel
+    convt16 = True  # ConvTranspose2d(64 -> 64, 2x2, stride 2) forward in 16-bit storage through its own kernel (off: the generic parity-class launch)
 
     def _convt16_panel(self, name, ct):
         w = ct.weight
@@ -807,7 +759,7 @@ class Engine:
                              lambda: torch.empty(self.L.dbn_convt16_panel_bytes(), device=w.device, dtype=torch.uint8),
                              lambda panel: check(self.L.dbn_convt16_pack(self.kind, w.data_ptr(), panel.data_ptr(), self.stream), 'convt16_pack'))
 
-    head16 = os.environ.get('DBN_HEAD16', '1') == '1'  # inference, 16-bit storage: ConvT -> BN -> ReLU -> ConvT -> sigmoid of both branches in ONE launch
+    head16 = True  # inference, 16-bit storage: ConvT -> BN -> ReLU -> ConvT -> sigmoid of both branches in ONE launch
 
     def _convt16(self, name, x, ct, out_name, bn_name=None, bn=None):
         """None when the layer does not take the 16-bit ConvT kernel; else (y, scale, shift) — scale / shift None without a BatchNorm."""
@@ -895,7 +847,6 @@ class Engine:
         L = self.L
         rows = L.dbn_winograd_rows(N, H, W)
         a = dict(y=None, zmask=None, msc=None, msh=None, mean=None, rstd=None, part=None, y2=None, mean2=None, rstd2=None, part2=None)
-        fin = None
         if consumer is not None:
             bn_name, y, zmask = consumer[:3]
             second = consumer[3] if len(consumer) > 3 else None
@@ -908,21 +859,6 @@ class Engine:
                 assert zmask is not None and second[1].shape == y.shape
                 a.update(y2=second[1], mean2=self.bufs[second[0] + '/mean'], rstd2=self.bufs[second[0] + '/rstd'],
                          part2=self.fbuf(second[0] + '/bnb_part', 2 * Cd * rows))
-            if self.bnb_finalize_in_kernel:
-                G = self.grad_views
-                cnt = self.bufs.get(bn_name + '/bnb_cnt')
-                ncnt = L.dbn_igemm_bn_final_counters(rows, Cd)
-                if cnt is None or cnt.numel() != ncnt or cnt.device != self.flat.device:
-                    cnt = torch.zeros(ncnt, device=self.flat.device, dtype=torch.int32)  # (the kernels leave them zero)
-                    self.bufs[bn_name + '/bnb_cnt'] = cnt
-                grp = self.fbuf(bn_name + '/bnb_grp', L.dbn_igemm_bn_final_group_floats(rows, Cd))
-                c1c2 = self.fbuf(bn_name + '/bnb_c1c2', 2 * Cd)
-                fin = _lib.BnbFinal(cnt.data_ptr(), grp.data_ptr(), c1c2.data_ptr(), G[bn_name + '.weight'].data_ptr(),
-                                    G[bn_name + '.bias'].data_ptr(), None, None, None, self.grad_scale)
-                if second is not None:
-                    c1c2b = self.fbuf(second[0] + '/bnb_c1c2', 2 * Cd)
-                    fin.c1c2_2, fin.dgamma_2, fin.dbeta_2 = (c1c2b.data_ptr(), G[second[0] + '.weight'].data_ptr(),
-                                                             G[second[0] + '.bias'].data_ptr())
         if self.prof:  # (FLOPs the MFMA pipe executes: see _winograd_conv)
             # algorithmic bytes: dy + dx once, + the operands of the fused BatchNorm-backward sums (y, a separate ReLU mask, a second BatchNorm's
             # y) and the accumulated-onto dx, once each
@@ -930,14 +866,14 @@ class Engine:
             self.prof.begin('winograd_f32_kernel', 2.0 * N * H * W * O * Cd * 4, 4.0 * N * H * W * (O + Cd * (1 + extra)), 'dgrad ' + name)
         check(L.dbn_winograd_dgrad_bnsums_f32(dy.data_ptr(), up.data_ptr(), dx.data_ptr(), N, H, W, O, Cd, int(accumulate), _p(a['y']),
                                               _p(a['zmask']), _p(a['msc']), _p(a['msh']), _p(a['mean']), _p(a['rstd']), _p(a['part']),
-                                              _p(a['y2']), _p(a['mean2']), _p(a['rstd2']), _p(a['part2']),
-                                              ctypes.byref(fin) if fin is not None else None, self.stream), 'winograd dgrad ' + name)
+                                              _p(a['y2']), _p(a['mean2']), _p(a['rstd2']), _p(a['part2']), None, self.stream),
+              'winograd dgrad ' + name)
         if self.prof:
             self.prof.end()
         if consumer is not None:
-            self._bnb_sums[consumer[0]] = (c1c2, -1) if fin is not None else (a['part'], rows)
+            self._bnb_sums[consumer[0]] = (a['part'], rows)
             if len(consumer) > 3 and consumer[3] is not None:
-                self._bnb_sums[consumer[3][0]] = (c1c2b, -1) if fin is not None else (a['part2'], rows)
+                self._bnb_sums[consumer[3][0]] = (a['part2'], rows)
 
     def conv_dgrad(self, name, dy, conv, dx, accumulate, version=None, consumer=None):
         """consumer: see _igemm — the BatchNorm that will consume dx, when this call is dx's last writer."""
@@ -963,13 +899,9 @@ class Engine:
             self.prof.end()
 
     # Slab reductions of the weight gradients as ONE grouped launch per gradient stage (dbn_wgrad_reduce_many) instead of one small
-    # launch behind every matrix kernel (round-3 review: 34 launches, 0.46 ms of work, 4.6 ms in flight on the side stream).
-    # Built, bit-identical (tested), measured on one box in interleaved runs and OFF: every layer then needs its OWN slab until
-    # the grouped launch runs (1.7 GB at bs16 640^2), while the per-layer form re-uses ONE <= 50 MB scratch that never leaves
-    # the 256 MB Infinity Cache — f32 545.6 -> 542.1 images/s, bf16 1667 -> 1340-1420 (profiles/r04_ab_grouped_reduce.txt).  The long
-    # in-flight time of the small reductions costs nothing: they run beside MFMA kernels on a stream that is not the critical path.
-    defer_wgrad_reduce = os.environ.get('DBN_DEFER_REDUCE', '0') == '1'
-    winograd_wgrad = os.environ.get('DBN_WINOGRAD_WGRAD', '1') == '1'  # (A/B switch; off: the direct kernels of wgrad_kernels.h)
+    # launch behind every matrix kernel.  Bit-identical (tested); off: measured slower.
+    defer_wgrad_reduce = False
+    winograd_wgrad = True  # (off: the direct kernels of wgrad_kernels.h)
 
     def wgrad(self, name, sm, big, O, I, k, stride, pad, gview, defer=False, big_act=None):
         """defer: the gradient is only needed by the optimizer / the gradient exchange, so its slab reduction may wait for
@@ -994,11 +926,8 @@ class Engine:
                 check(self.L.dbn_winograd_wgrad_f32(3, *wargs), 'winograd wgrad ' + name)
             return
         assert big_act is None, name  # (lazy_act() defers an activation only where this branch is taken)
-        # reductions on their own stream (see reduce_stream): only for gradients no kernel of this pass reads, on the side stream
-        async_reduce = (defer and self.reduce_stream and self._in_side and self.prof is None and not self.defer_wgrad_reduce
-                        and not torch.cuda.is_current_stream_capturing())
         defer = defer and self.defer_wgrad_reduce and self.prof is None and Cb % 64 == 0
-        slab = self.scratch('_wgrad_slab/' + name if defer else ('_wgrad_slab@%d' % self._slab_k if async_reduce else '_wgrad_slab'),
+        slab = self.scratch('_wgrad_slab/' + name if defer else '_wgrad_slab',
                             self.L.dbn_wgrad_slab_floats_hw(N, Ho, Wo, O, H, W, Cb, k, k, 4 if self.at == 0 else 2))
         at, smp, bigp = self.at, sm.data_ptr(), big.data_ptr()
         if self._use_planes and sm.dtype == torch.float32 and big.dtype == torch.float32:
@@ -1028,39 +957,8 @@ class Engine:
                 check(self.L.dbn_wgrad_reduce_describe(*args[:-1], ctypes.byref(job)), 'wgrad reduce describe ' + name)
                 self._reduce_job_cache[key] = job
             self._reduce_pending.append((key, job))
-        elif async_reduce:
-            side = torch.cuda.current_stream(self.flat.device)
-            free = self._slab_free[self._slab_k]
-            if free is not None:  # this slab's previous reduction (two weight gradients ago) has read it
-                side.wait_event(free)
-            check(self.L.dbn_wgrad_phase_t(1, *args), 'wgrad ' + name)
-            filled = torch.cuda.Event()
-            filled.record(side)
-            if self._side2 is None or self._side2.device != self.flat.device:
-                self._side2 = torch.cuda.Stream(device=self.flat.device)
-            self._side2.wait_event(filled)
-            with torch.cuda.stream(self._side2):
-                check(self.L.dbn_wgrad_phase_t(2, *args[:-1], self._side2.cuda_stream), 'wgrad reduce ' + name)
-                done = torch.cuda.Event()
-                done.record(self._side2)
-            self._slab_free[self._slab_k] = done
-            self._slab_k ^= 1
-            self._side2_used = True
         else:
             check(self.L.dbn_wgrad_t(*args), 'wgrad ' + name)
-
-    # The slab reduction of a weight gradient (34 launches of 5-260 us per step, latency-bound: 0.46 ms alone) sits BETWEEN the matrix
-    # kernels of the side stream, and since the Winograd convs shortened the main stream the side stream is what the step's end waits
-    # for (round-4 trace: wgrad_reduce64 1.4 ms in flight, 0.9 ms of it with nothing else running).  reduce_stream = True runs the
-    # reductions of gradients that only the optimizer reads on a THIRD stream behind their matrix kernel, over two alternating slab
-    # scratches (both stay in the Infinity Cache).  Built, bit-identical, measured on one box and OFF: f32 614.7 -> 606.7 images/s,
-    # bf16 1600 -> 1390-1470 (three extra event / wait calls per weight gradient on the host, and the reductions now compete with the
-    # NEXT matrix kernel instead of running in its shadow at the end); not used under hipGraph capture (cross-stream events created
-    # inside a capture crashed capture_end on ROCm 7.2).
-    reduce_stream = os.environ.get('DBN_REDUCE_STREAM', '0') == '1'
-    _side2 = None
-    _side2_used = False
-    _slab_k = 0
 
     def flush_wgrad_reduces(self):
         """The deferred slab reductions as ONE launch on the side stream (behind the matrix kernels that filled the slabs)."""
@@ -1086,14 +984,8 @@ class Engine:
     # BatchNorm backward of the main stream (or at the end of the pass).  The side stream waits for everything the main stream has
     # enqueued by then — i.e. also for this layer's data gradient — so the weight gradient runs beside the HBM-bound BatchNorm pass
     # and the next layer's data gradient instead of beside its own layer's data gradient (two MFMA kernels side by side are zero-sum,
-    # an MFMA kernel beside an HBM-bound one hides it).  Round 3 measured this as a loss (538 -> 532 images/s) when the data
-    # gradients were the longer kernels; with the Winograd data gradients the main stream's BatchNorm passes had become exposed
-    # (1.28 ms of bn_bwd_apply with no MFMA kernel in flight, round-4 trace).  Measured on one box, interleaved: exact fp32 629 vs
-    # 633 images/s (off is better: default off there); bf16 1620-1630 vs 1430-1500 (on is better, and equal to the round-3 tree on the
-    # same box — the bf16 step with immediate launches is bimodal from process to process, 1170 / 1445 / 1670 images/s for the SAME
-    # library, profiles/r04_late_wgrad.txt — the late order has only shown the fast mode): default on for the 16-bit storage modes.
-    late_wgrad = os.environ.get('DBN_LATE_WGRAD', '')  # '' = in the 16-bit storage modes only (measured, see above); '0' / '1' force
-
+    # an MFMA kernel beside an HBM-bound one hides it).  In the 16-bit storage modes only: in exact fp32 the immediate launch measured
+    # faster.
     def _flush_wgrads(self):
         if self._wgrad_fifo:
             fifo, self._wgrad_fifo = self._wgrad_fifo, []
@@ -1109,7 +1001,7 @@ class Engine:
                            big_act=x_act)
                 if conv.bias is not None and name + '.bias' not in self._bias_done:
                     self.col_sum(dy, self.grad_views[name + '.bias'])
-        late = self.late_wgrad == '1' or (self.late_wgrad == '' and self.at != 0)
+        late = self.at != 0
         if late and self.overlap_wgrad and not self._in_side and self.prof is None:
             self._wgrad_fifo.append(launch)
         else:
@@ -1258,14 +1150,10 @@ class Engine:
     # weight gradient) the activation tensor is never written — the kernels apply relu(fma(y, scale, shift)) while they stage their
     # patches, with bn_apply's own arithmetic (bit-identical results).  Exact-fp32 mode only (the 16-bit kernels bring their tiles to
     # LDS by DMA: nothing passes through registers).  The BatchNorm backward takes its ReLU mask from y already (mask 'self').
-    apply_on_load = os.environ.get('DBN_APPLY_ON_LOAD', '1') == '1'
+    apply_on_load = True
     # The FPN output conv's level 0 (a plain 3x3 conv of p2, 53 % of the pyramid's FLOPs) through the Winograd kernel, levels 1-3 added by
-    # the pyramid launch (dbn_pyramid_conv_from_t): same results to fp32 rounding (test_pyramid_conv_on_a_winograd_level_0), measured
-    # on one box in interleaved runs: 702.6 / 703.8 / 703.2 images/s without, 709.6 / 708.0 / 708.6 with (+0.8 %: the 64 -> 256 Winograd
-    # launch re-stages every patch four times and the second launch re-reads the 164 MB output it accumulates into, which eats most of the
-    # 2.25x).  (A first measurement had shown "no difference": a wrong shape check had kept the switch from taking effect — the test
-    # found it.)
-    fpn_level0_winograd = os.environ.get('DBN_FPN_LV0_WINOGRAD', '1') == '1'
+    # the pyramid launch (dbn_pyramid_conv_from_t): same results to fp32 rounding (test_pyramid_conv_on_a_winograd_level_0).
+    fpn_level0_winograd = True
 
     def lazy_act(self, y, convs, train):
         """True when relu(bn(y)) may stay unwritten: every conv in `convs` (all read it as their input) runs as a Winograd conv forward
@@ -1279,7 +1167,7 @@ class Engine:
         """mask: None (no ReLU), 'self' (ReLU directly on this BN's output: recomputed from y with the
         forward's scale/shift, nothing extra is read), or a tensor (saved activation whose sign gates).
         conv_bias: name of the bias parameter of the conv that produced y (its gradient = column sums of dy)."""
-        self._flush_wgrads()  # (late_wgrad: the queued weight gradients start beside this HBM-bound pass)
+        self._flush_wgrads()  # (conv_wgrad: the queued weight gradients start beside this HBM-bound pass)
         C = y.shape[-1]
         M = y.numel() // C
         dy = self.buf(dy_name, *y.shape)
@@ -1509,8 +1397,8 @@ class Engine:
         return out
 
     # ---- the stem in 16-bit storage (round 5, csrc/stem16.hip): conv 7x7 / 2 on a PACKED, zero-bordered 4-channel image instead of 16-channel
-    # blocks with 13 zero channels (K = 224 instead of 784, no 16-channel copy of the input).  DBN_STEM16=0: the generic 16-bit loop.
-    stem16 = os.environ.get('DBN_STEM16', '1') == '1'
+    # blocks with 13 zero channels (K = 224 instead of 784, no 16-channel copy of the input).  Off: the generic 16-bit loop.
+    stem16 = True
 
     def _stem16_ok(self, conv, N, H, W):
         return (self.stem16 and self.at != 0 and (conv.k, conv.stride, conv.padding, conv.cin, conv.cout) == (7, 2, 3, 3, 64) and conv.bias is None
@@ -1599,9 +1487,8 @@ class Engine:
         vconv, ver2 = self._cols_conv(name + '.conv2', conv)
         return self.conv_bn(name + '.conv2', cols, vconv, out_name, bn_name, bn, train, version=ver2)
 
-    flush_before_pool = os.environ.get('DBN_FLUSH_BEFORE_POOL', '1') == '1'
-    dcn_gather = os.environ.get('DBN_DCN_GATHER', '1') == '1'  # the sampling adjoint as a gather (0: round 3's fixed-point scatter)
-    dcn_gather_max_offset = float(os.environ.get('DBN_DCN_GATHER_MAX_OFFSET', '16'))  # ... while the previous step's max |offset| of the layer is below this
+    dcn_gather = True  # the sampling adjoint as a gather (off: round 3's fixed-point scatter)
+    dcn_gather_max_offset = 16.0  # ... while the previous step's max |offset| of the layer is below this
     _dcn_table = _dcn_host = _dcn_event = None
 
     def _dcn_read_back(self):
@@ -1752,18 +1639,7 @@ class Engine:
             cur = self.conv_bn_act_eval(cname, cur, conv, name + ('/out' if last else '/z%d' % (i + 1)), bn, relu=True, res=res if last else None)
         return cur
 
-    eval_downsample_beside = os.environ.get('DBN_EVAL_DOWNSAMPLE_BESIDE', '1') == '1'
-
-    # 16-bit storage: level 0 of the pyramid conv through the pixel-patch kernel.  0: off (default); 1: in train mode; 2: in inference too.
-    # Measured: `tools/cfg_timing.py` (eager loop, host-paced) bf16 16 x 640^2 12.02 -> 11.5 ms, twice — but bench.py's step (resident inputs,
-    # collector off, GPU-paced), interleaved on one box: 1655 / 1654 images/s without it, 1643 / 1638 with it; cfg5 fp16 inference 14.95 ->
-    # 15.7 ms (the second pass over the 1.7 GB output — write, read, write — costs more than the faster level 0 saves).  Off.
-    fpn_level0_patch = int(os.environ.get('DBN_FPN_LV0_PATCH', '0'))
-
-    def _fpn_level0_patch_ok(self, z0, Co, train=False):
-        N, H, W, Cg = z0.shape
-        return (self.fpn_level0_patch >= (1 if train else 2) and self.at != 0 and self.ns == 1 and Cg % 32 == 0 and H % 8 == 0 and W % 16 == 0
-                and Co % 128 == 0)
+    eval_downsample_beside = True  # inference: a block's projection shortcut on the second stream, beside conv1
 
     def _fpn_conv_eval(self, name, conv, zs, out_name, bn):
         """Inference form of the FPN output conv + BatchNorm + ReLU (segmentation_body.py:55-61,75-76): the pyramid conv on the combined
@@ -1777,15 +1653,7 @@ class Engine:
         wpk = [self.pack('%s#f%d' % (fname, g), wds[g], 1, 1 << g, version=wver) for g in range(4)]
         lv0 = _VirtualConv(Cg, Co, 3, 1, 1, wds[0], vconv.bias)
         first = int(self.fpn_level0_winograd and wds[0].shape[0] == Cg and self._winograd_ok(zs[0], lv0))
-        if self._fpn_level0_patch_ok(zs[0], Co):  # 16-bit storage: level 0 through the pixel-patch kernel (see _fpn_conv_forward)
-            if self.prof:
-                self._prof_igemm(N * H * W, Co, 2.0 * N * H * W * Co * Cg * 9, 'fwd %s level 0' % name, 1, (N, H, W, Cg, H, W, 3, 1, 1))
-            check(self.L.dbn_igemm_act_t(self.at, self.ns, zs[0].data_ptr(), wpk[0].data_ptr(), vconv.bias.data_ptr(), None, 0, z.data_ptr(), N, H, W,
-                                         Cg, H, W, Co, 3, 3, 1, 1, 1, 0, self.stream), 'igemm fpn level 0')
-            if self.prof:
-                self.prof.end()
-            first = 1
-        elif first:
+        if first:
             up = self._winograd_panel(fname + '#lv0', wds[0], Cg, dgrad=1, version=wver)
             if self.prof:
                 self.prof.begin('winograd_f32_kernel', 2.0 * N * H * W * Co * Cg * 4, 0.0, 'fwd %s level 0' % name)
@@ -1808,8 +1676,8 @@ class Engine:
     # The head tail's backward and the BatchNorm backward in front of each branch's last ConvT as ONE native call
     # (dbn_head_tail_bn_bwd_t): the two 64-channel gradients at half resolution between them (`binarize/dz1`, `thresh/dz1`) are formed
     # again inside the BatchNorm apply pass and are neither allocated, written nor read.  Same bits as the unfused sequence
-    # (tests/test_head_bn_bwd_gpu.py); DBN_HEAD_BWD_FUSED=0: the unfused sequence (the A/B switch).
-    head_bwd_fused = os.environ.get('DBN_HEAD_BWD_FUSED', '1') == '1'
+    # (tests/test_head_bn_bwd_gpu.py); off: the unfused sequence.
+    head_bwd_fused = True
     head_bwd_fused_ats = (0, 1, 2)  # storage types that take the fused path (the bit-identity test runs over exactly these)
 
     def _head_tail_args(self, out, dpreds):
@@ -1885,7 +1753,6 @@ class Engine:
         self._dcn_read_back()
         # (a pass that raised between queueing and flushing must not leave launches holding the PREVIOUS batch's tensors behind)
         self._wgrad_fifo, self._reduce_pending = [], []
-        self._slab_free = [None, None]  # (the previous pass's reductions were joined: no event of it is waited for again)
         out = self.saved_out  # head output before the (optional) final resample
         dpreds = dpreds.contiguous()
         assert dpreds.shape == (N, 3, H, W)
@@ -1979,7 +1846,6 @@ class Engine:
         self.flush_wgrad_reduces()  # FPN + head (one grouped launch per gradient stage: train.GRAD_STAGES)
         if self.grad_ready_hook is not None:  # every FPN / head gradient kernel has been enqueued
             with self.side_stream():  # announced from the side stream (it has waited for the main one): main is not stalled
-                self._side_waits_for_reductions()
                 self.grad_ready_hook('segmentation')
         # backbone, deepest stage first; dC[...] already holds the FPN contribution
         bb = m.backbone
@@ -2002,11 +1868,9 @@ class Engine:
                 self.flush_wgrad_reduces()
             if self.grad_ready_hook is not None and li >= 3:
                 with self.side_stream():
-                    self._side_waits_for_reductions()
                     self.grad_ready_hook('layer%d' % li)
         y0 = B['stem/y']
-        if self.flush_before_pool:
-            self._flush_wgrads()  # (late order: layer1's last weight gradient starts beside the max-pool backward, not behind it — round-5 trace: it had waited 218 us)
+        self._flush_wgrads()  # (late order: layer1's last weight gradient starts beside the max-pool backward, not behind it)
         if self.pool_argmax and self._pool_arg_generation == self.generation:
             # pool + ReLU + BatchNorm backward from the recorded argmax: sums over the pooled tensors, then ONE pass y -> dy
             dy0 = self.buf('stem/dy', *y0.shape)
@@ -2049,8 +1913,8 @@ class Engine:
 
     backwards_since_clear = 0
     # the stem's max-pool with a recorded argmax (PyTorch's first-maximum rule; csrc/pointwise.hip: bnrelu_maxpool_fwd_arg_kernel).
-    # DBN_POOL_ARGMAX=0: round 4's pair (gradient to every position that ties with the maximum, a gradient tensor at the conv's resolution)
-    pool_argmax = os.environ.get('DBN_POOL_ARGMAX', '1') == '1'
+    # Off: round 4's pair (gradient to every position that ties with the maximum, a gradient tensor at the conv's resolution)
+    pool_argmax = True
     _pool_arg_generation = -1
     fpn_structured = True  # FPN output conv per upsample level (forward and backward) instead of over the concat
     fpn_one_launch = True  # forward: the four levels in one launch (dbn_pyramid_conv_f32) instead of four accumulating ones
@@ -2087,18 +1951,7 @@ class Engine:
             # through the Winograd kernel (2.25x fewer matrix FLOPs) and the pyramid launch adds levels 1-3 onto it
             lv0 = _VirtualConv(Cg, Co, 3, 1, 1, wds[0], conv.bias)
             first = int(self.fpn_level0_winograd and not self._use_planes and wds[0].shape[0] == Cg and self._winograd_ok(zs[0], lv0))
-            # 16-bit storage (round 5): level 0 — 53 % of the pyramid's FLOPs — as a mode-1 3x3 / stride-1 launch on the level-0 panel, which
-            # takes the pixel-patch kernel (0.3-0.36 of the 16-bit matrix peak; the pyramid's generic loop: 0.2), levels 1-3 added onto it
-            first16 = self._fpn_level0_patch_ok(zs[0], Co, train)
-            if first16:
-                if self.prof:
-                    self._prof_igemm(N * H * W, Co, 2.0 * N * H * W * Co * Cg * 9, 'fwd %s level 0' % name, 1, (N, H, W, Cg, H, W, 3, 1, 1))
-                self._igemm('igemm fpn level 0', zs[0].data_ptr(), wpk[0].data_ptr(), _p(conv.bias), y.data_ptr(), N, H, W, Cg, H, W, Co, 3, 3, 1, 1, 1,
-                            0, 0)
-                if self.prof:
-                    self.prof.end()
-                first = 1
-            elif first:
+            if first:
                 # (wds[0][ci][co][u][v] = W[co][ci][2-u][2-v]: its data-gradient panel is the forward conv of W's first Cg input channels)
                 up = self._winograd_panel(name + '#lv0', wds[0], Cg, dgrad=1, version=wver)
                 if self.prof:

@@ -100,7 +100,7 @@ def test_winograd_conv_bn_with_the_statistics_folded_in_kernel(shape):
 
 
 def test_train_step_with_the_statistics_folded_in_kernel_equals_the_default_step():
-    """Engine.bn_final_in_kernel (DBN_BN_FINAL=1; off by default: measured slower): one train step of ResNet18-FPN-DBHead with
+    """Engine.bn_final_in_kernel (off by default: measured slower, DESIGN sections 14.4 and 31): one train step of ResNet18-FPN-DBHead with
     every conv + BatchNorm folding its own statistics against the default step (finalize kernels) — losses, maps and gradients to fp64
     merge-order noise."""
     from db_text_minimal_amd import DBLoss, DBTextModel, DBTrainer, FusedAdam

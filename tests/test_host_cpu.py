@@ -118,6 +118,20 @@ def test_product_package_never_imports_the_oracle():
                 assert 'oracle' not in src.replace('the CPU oracle', ''), os.path.join(dirpath, f)
 
 
+def test_every_environment_name_the_package_reads_is_documented():
+    """Every DBN_* name that a module of the package reads through os.environ is listed in INTEGRATION.md."""
+    pkg = os.path.join(ROOT, 'db_text_minimal_amd')
+    reads = re.compile(r"""os\.environ(?:\.get\(|\.pop\(|\[)\s*['"](DBN_[A-Z0-9_]+)['"]|['"](DBN_[A-Z0-9_]+)['"]\s+(?:not\s+)?in\s+os\.environ""")
+    names = set()
+    for f in sorted(os.listdir(pkg)):
+        if f.endswith('.py'):
+            for m in reads.finditer(open(os.path.join(pkg, f)).read()):
+                names.add(m.group(1) or m.group(2))
+    assert {'DBN_POISON', 'DBN_FOLD_EVAL_BN', 'DBN_LIB_PATH', 'DBN_STEP_GRAPH'} <= names, names  # (the expression still finds the reads)
+    documented = set(re.findall(r'DBN_[A-Z0-9_]+', open(os.path.join(ROOT, 'INTEGRATION.md')).read()))
+    assert not names - documented, sorted(names - documented)
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, 'LIB_PATH', str(tmp_path / 'nope.so'))
     monkeypatch.setattr(_lib, '_lib', None)
