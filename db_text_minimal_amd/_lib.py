@@ -45,6 +45,8 @@ SIGNATURES = {
     'dbn_resize_linear_norm_u8': 'plppiii' + 'fff' + 'pp',
     'dbn_perspective_maps': 'piiipp',
     'dbn_warp_perspective_u8': 'plppiiiplp',
+    'dbn_polygon_ribbons': 'ppiiiipppp',
+    'dbn_rectify_u8': 'plpppiiiiplp',
     'dbn_draw_strokes': 'pplpipliiiip',
     'dbn_draw_glyphs': 'pplpiplpipliiiiip',
     'dbn_render_minmax': 'ppilplliifpp',

@@ -6,7 +6,8 @@
   greedy_decode(logits, mode, lengths)         predict()'s argmax, softmax, maximum probability, cumprod and the CTC /
                                                attention collapse: (codes, count, score) on the device, two launches
   CTCLabelConverter / AttnLabelConverter       codes -> strings, from one device-to-host copy
-  recognize_words(images, boxes, model, ...)   crop_words -> words_to_input -> model -> greedy_decode -> strings
+  recognize_words(images, boxes, model, ...)   crop_words (rectify_words for polygons=) -> words_to_input -> model ->
+                                               greedy_decode -> strings
 
 Pinned: the grey formula against PIL's convert('L') and the normalisation against torch's ToTensor arithmetic (on the
 CPU, tests/test_recognise_cpu.py); the decode against a numpy restatement that equals the reference's torch ops.
@@ -17,7 +18,7 @@ import torch
 
 from ._lib import check, lib
 from .augment import _stream
-from .word_crops import SIZE, crop_words
+from .word_crops import SIZE, crop_words, rectify_words
 
 _INT_MAX = 2 ** 31 - 1
 _AT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # DBN_AT_* of include/dbnet_hip.h
@@ -173,15 +174,19 @@ def _box_rows(boxes):
 
 
 def recognize_words(images, boxes, model, converter, prediction='CTC', batch_size=512, batch_max_length=25, rgb=False, size=SIZE,
-                    scores=None, min_score=None):
+                    scores=None, min_score=None, polygons=None, segments=32, ends='auto'):
     """From images and detected boxes to strings: crop_words -> words_to_input -> model -> greedy_decode -> converter.decode.
 
-    images, boxes, size, scores, min_score: as crop_words takes them.  Or ready crops: images = a uint8 device tensor
-    [K, h, w, 3] with boxes = None.  model: the user's recogniser, called under no_grad in chunks of batch_size as the
-    reference calls it, with text_for_pred a zero LongTensor [b, batch_max_length + 1]: model(image, text_for_pred) for
+    images, boxes, size, scores, min_score: as crop_words takes them.  Or polygons= (with boxes = None) instead of boxes:
+    images, polygons, size, scores, min_score, segments, ends as rectify_words takes them, which then cuts the crops.  Or
+    ready crops: images = a uint8 device tensor [K, h, w, 3] with boxes = None.
+    model: the user's recogniser, called under no_grad in chunks of batch_size as the reference calls it, with text_for_pred a zero LongTensor [b, batch_max_length + 1]: model(image, text_for_pred) for
     prediction 'CTC', model(image, text_for_pred, is_train=False) for 'Attn'; it returns logits [b, T, C].
-    Returns, per image, a list of {'box': the box row (int16 [4, 2]), 'pred': str, 'score': float} in box order; for ready
-    crops one flat list with 'box': None.  One device-to-host copy for all words."""
+    Returns, per image, a list of {'box': the box row (int16 [4, 2]), 'pred': str, 'score': float} in box order ('box': the
+    polygon as given, [P, 2], for polygons=); for ready crops one flat list with 'box': None.  One device-to-host copy for
+    all words."""
+    if boxes is not None and polygons is not None:
+        raise ValueError('boxes or polygons, not both')
     if 'CTC' in prediction:
         mode = 'ctc'
     elif 'Attn' in prediction:
@@ -191,7 +196,12 @@ def recognize_words(images, boxes, model, converter, prediction='CTC', batch_siz
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError('batch_size must be positive')
-    if boxes is None:
+    if polygons is not None:
+        polygons = list(polygons)
+        crops, index = rectify_words(images, polygons, size, scores, min_score, segments, ends)
+        rows = [[np.asarray(p) for p in (ps[0] if isinstance(ps, tuple) and len(ps) == 2 else ps)] for ps in polygons]
+        n_images = 1 if isinstance(images, torch.Tensor) else len(images[1])
+    elif boxes is None:
         crops, index, rows, n_images = images, None, None, None
     else:
         crops, index = crop_words(images, boxes, size, scores, min_score)

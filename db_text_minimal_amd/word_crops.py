@@ -12,6 +12,16 @@
 The maps restate OpenCV 4.2's getPerspectiveTransform (the 8 x 8 system solved by its LU) and its 3 x 3 invert; the pixels
 restate WarpPerspectiveInvoker + remapBilinear on 8-bit data.  PARITY UNPINNED against cv2 itself, which could not be run
 here: its SIMD / IPP paths, and whether the restated LU and invert match it in every operation.
+
+The reference stops there (test_ocr.py:162 crops only `if not opt.is_output_polygon`).  For polygon output, its default:
+
+  polygon_ribbons(polygons, segments, ends)          host: the ribbon of every polygon (centre line and cross-sections,
+                                                     fp64 -> int32 units of 1 / 1024 px), one C call
+  rectify_words(images, polygons, size, ...)         device: every kept polygon straightened into an h x w crop, one launch
+                                                     (csrc/rectify.hip rectify_u8), and their (image, polygon row) index
+  rectify_from_ribbons(images, knots, valid, ...)    the device half alone, on knots of the caller's choosing
+
+What a straightened polygon is is THIS PROJECT'S DEFINITION, in exact integers on the device.
 """
 import numpy as np
 import torch
@@ -21,6 +31,8 @@ from .augment import _MAX_SIDE, _check_shape, _offsets, _packed, _stream, _to_de
 
 SIZE = (32, 100)  # (h, w) of test_ocr.py / test_webcam.py / utils.py
 _WP_PX, _INT_MAX = 1024, 2 ** 31 - 1  # output pixels per workgroup of warp_perspective_u8
+_MIN_SEG, _MAX_SEG, _MAX_VERTS, _MAX_COORD, _HOST_THREADS = 4, 64, 256, 2.0 ** 20, 16  # dbn_polygon_ribbons
+_RC_PX, _RC_MAX_HW = 1024, 2 ** 30  # dbn_rectify_u8: output pixels per workgroup, the largest crop
 
 
 def _size(size):
@@ -148,3 +160,140 @@ def crop_words(images, boxes, size=SIZE, scores=None, min_score=None, device=Non
     check(lib().dbn_warp_perspective_u8(src.data_ptr(), src.numel(), d.data_ptr(), m.data_ptr(), K, h, w, crops.data_ptr(), crops.numel(),
                                         _stream(dev)), 'warp_perspective_u8')
     return crops, index
+
+
+# ---- word images of text polygons (csrc/rectify.hip; this project's definition) ------------------------
+def _segments(segments):
+    s = int(segments)
+    if s != segments or not (_MIN_SEG <= s <= _MAX_SEG):
+        raise ValueError('segments must be an integer in %d .. %d, got %r' % (_MIN_SEG, _MAX_SEG, segments))
+    return s
+
+
+def _polygon(p, ends):
+    p = np.asarray(p)
+    if p.ndim != 2 or p.shape[1] != 2 or p.dtype.kind not in 'iuf':
+        raise ValueError('a polygon must be a numeric [P, 2] array, got shape %s' % (p.shape, ))
+    n = p.shape[0]
+    if not (3 <= n <= _MAX_VERTS):
+        raise ValueError('a polygon has 3 .. %d vertices, got %d' % (_MAX_VERTS, n))
+    if ends == 'half' and n % 2:
+        raise ValueError("ends='half' needs an even number of vertices, got %d" % n)
+    p = p.astype(np.float64)
+    if not (np.abs(p) <= _MAX_COORD).all():  # false for a NaN
+        raise ValueError('polygon coordinates must be finite and within +-2^20')
+    return p
+
+
+def polygon_ribbons(polygons, segments=32, ends='auto', return_info=False):
+    """The ribbon of every polygon, the host half of rectify_words (dbn_polygon_ribbons: one C call, fp64, up to 16 threads).
+
+    polygons: a sequence of [P, 2] (x, y) arrays in border order, either orientation, 3 <= P <= 256, finite and within
+    +-2^20.  The word's two ends are two of the 2P boundary points (vertices and edge midpoints): with ends='auto' the
+    non-adjacent pair whose two boundary chains lie closest to each other (detector output), with ends='half' the middles
+    of the edges (v[P-1], v[0]) and (v[P/2-1], v[P/2]), the annotation order of Total-Text and CTW1500 (first half one side,
+    second half the other side back).  Returns (knots int32 [K, S + 1, 4], valid uint8 [K]): per knot the centre-line point
+    and the cross-section vector (width times unit normal) in units of 1 / 1024 pixel; valid = 0 (zero knots) for a
+    polygon without area, width or length[, and with return_info a dict: ends int32 [K, 2] (the boundary-point indices
+    i, j), E, width, length fp64 [K]]."""
+    S = _segments(segments)
+    if ends not in ('auto', 'half'):
+        raise ValueError("ends must be 'auto' or 'half', got %r" % (ends, ))
+    polys = [_polygon(p, ends) for p in polygons]
+    K = len(polys)
+    knots, valid = np.zeros((K, S + 1, 4), np.int32), np.zeros(K, np.uint8)
+    found, info = np.zeros((K, 2), np.int32), np.zeros((K, 3), np.float64)
+    if K:
+        xy = np.ascontiguousarray(np.concatenate(polys))
+        offs = _offsets([len(p) for p in polys])
+        check(lib().dbn_polygon_ribbons(xy.ctypes.data, offs.ctypes.data, K, S, int(ends == 'half'), _HOST_THREADS, knots.ctypes.data,
+                                        valid.ctypes.data, found.ctypes.data, info.ctypes.data), 'polygon_ribbons')
+    if return_info:
+        return knots, valid, dict(ends=found, E=info[:, 0].copy(), width=info[:, 1].copy(), length=info[:, 2].copy())
+    return knots, valid
+
+
+def select_polygons(polygons, scores=None, min_score=None):
+    """The polygons rectify_words straightens: per image a list of [P, 2] arrays (or the (polygons, scores) pairs of
+    detect_polygons), those with a coordinate sum <= 0 dropped and, with min_score, those scoring below it: select_boxes'
+    rule.  -> (list of [P, 2] arrays, index int64 [K, 2] of (image, polygon row))."""
+    polygons = list(polygons)
+    pairs = [isinstance(p, tuple) and len(p) == 2 for p in polygons]
+    if any(pairs):
+        if not all(pairs):
+            raise ValueError('polygons mixes (polygons, scores) pairs with plain polygon lists')
+        if scores is None:
+            scores = [s for _, s in polygons]
+        polygons = [p for p, _ in polygons]
+    if scores is not None and len(scores) != len(polygons):
+        raise ValueError('%d score lists for %d images' % (len(scores), len(polygons)))
+    if min_score is not None and scores is None:
+        raise ValueError('min_score needs the scores')
+    kept, index = [], []
+    for n, ps in enumerate(polygons):
+        if min_score is not None and len(scores[n]) != len(ps):
+            raise ValueError('image %d has %d polygons and %d scores' % (n, len(ps), len(scores[n])))
+        for k, p in enumerate(ps):
+            p = np.asarray(p)
+            if p.size == 0 or p.sum() <= 0:
+                continue
+            if min_score is not None and float(scores[n][k]) < float(min_score):
+                continue
+            kept.append(p)
+            index.append((n, k))
+    return kept, np.array(index, np.int64).reshape(-1, 2)
+
+
+def rectify_from_ribbons(images, knots, valid, image_index, size=SIZE, device=None):
+    """The device half of rectify_words alone (dbn_rectify_u8, one launch): crop q is read from image image_index[q] along
+    the ribbon knots[q] (int32 [S + 1, 4], polygon_ribbons' layout, any values); valid[q] = 0 gives a zero crop.  images as
+    crop_words takes them.  -> uint8 [K, h, w, 3] on the device."""
+    h, w = _size(size)
+    packed, shapes = _images(images)
+    knots = np.ascontiguousarray(knots, dtype=np.int32)
+    if knots.ndim != 3 or knots.shape[2] != 4:
+        raise ValueError('knots must be int32 [K, S + 1, 4], got shape %s' % (knots.shape, ))
+    K, S = knots.shape[0], _segments(knots.shape[1] - 1)
+    valid = np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)
+    image_index = np.ascontiguousarray(image_index, dtype=np.int64).reshape(-1)
+    if valid.shape[0] != K or image_index.shape[0] != K:
+        raise ValueError('%d ribbons, %d valid flags, %d image indices' % (K, valid.shape[0], image_index.shape[0]))
+    if K and not (0 <= int(image_index.min()) and int(image_index.max()) < len(shapes)):
+        raise ValueError('image indices outside the %d images' % len(shapes))
+    # dbn_rectify_u8: h w <= 2^30 keeps the 64-bit pixel arithmetic exact for any int32 knots; the grid is one run of blocks
+    if h * w > _RC_MAX_HW or K * -(-h * w // _RC_PX) > _INT_MAX:
+        raise ValueError('%d crops of %d x %d are too many or too large for one call' % (K, h, w))
+    dev = torch.device(device) if device is not None else (packed.device if packed.is_cuda else torch.device('cuda', torch.cuda.current_device()))
+    if dev.type != 'cuda':
+        raise ValueError('rectify_words runs on a GPU device, not %s' % dev)
+    src = _packed(packed, shapes, dev)
+    crops = torch.empty((K, h, w, 3), device=dev, dtype=torch.uint8)
+    if K == 0:
+        return crops
+    src_off = _offsets([sh * sw * 3 for sh, sw in shapes])
+    hw = np.array(shapes, np.int64)[image_index]
+    desc = np.stack([src_off[image_index], hw[:, 0], hw[:, 1]], 1)
+    d, kn, va = _to_device(desc, dev), _to_device(knots, dev), _to_device(valid, dev)
+    check(lib().dbn_rectify_u8(src.data_ptr(), src.numel(), d.data_ptr(), kn.data_ptr(), va.data_ptr(), K, S, h, w, crops.data_ptr(),
+                               crops.numel(), _stream(dev)), 'rectify_u8')
+    return crops
+
+
+def rectify_words(images, polygons, size=SIZE, scores=None, min_score=None, segments=32, ends='auto', device=None):
+    """Every kept text polygon of every image straightened into an h x w word image, on the device: crop_words for curved
+    text.  The reference crops boxes only (test_ocr.py:162), so what a straightened polygon is is this project's
+    definition: the ribbon of polygon_ribbons, sampled with x = 0 on its start cap and y = 0 on its top
+    side, bilinearly with a zero border, in integers.  An axis-aligned rectangle of the crop's size is the plain slice, as
+    crop_words gives for that box.
+
+    images: as crop_words takes them.  polygons: per image a list of [P, 2] arrays in the images' pixel coordinates, or
+    the (polygons, scores) pairs of detect_polygons(..., dest_sizes=...).  Dropped: polygons whose coordinates sum to <= 0
+    and, with min_score, those scoring below it.  Returns (crops, index): crops uint8 [K, h, w, 3] on the device, index
+    int64 [K, 2] numpy of (image, polygon row).  One host call for the ribbons, one launch on the current stream."""
+    _size(size)
+    packed, shapes = _images(images)
+    kept, index = select_polygons(polygons, scores, min_score)
+    if index.size and int(index[:, 0].max()) >= len(shapes):
+        raise ValueError('polygons for %d images, but %d images' % (int(index[:, 0].max()) + 1, len(shapes)))
+    knots, valid = polygon_ribbons(kept, segments, ends)
+    return rectify_from_ribbons((packed, shapes), knots, valid, index[:, 0], size, device), index

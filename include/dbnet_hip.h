@@ -456,6 +456,29 @@ int dbn_perspective_maps(const float* quads, int K, int out_h, int out_w, double
 int dbn_warp_perspective_u8(const unsigned char* src, long src_bytes, const long long* desc, const double* inv, int K, int out_h, int out_w,
                             unsigned char* dst, long dst_bytes, void* stream);
 
+/* ---- word images of text polygons: a curved word straightened into out_h x out_w (csrc/rectify.hip,
+ *      db_text_minimal_amd/word_crops.py).  THIS PROJECT'S DEFINITION, the reference crops boxes only. ---- */
+/* host: the ribbons of K polygons, on min(K, 16, threads) threads.  Polygon k has the vertices xy[offs[k] .. offs[k + 1])
+ * (fp64 (x, y), border order, either orientation; offs[0] = 0), 3 .. 256 of them, finite and within +-2^20; half = 1 needs
+ * an even count.  Its 2n boundary points are the vertices and the edge midpoints (point 2i = vertex i).  half = 0: the ends
+ * are the non-adjacent pair i < j whose two chains, sampled at segments + 1 equal arclength fractions, have the smallest
+ * mean squared distance E (ties: the smallest (i, j)); half = 1: points 2n - 1 and n - 1.  knots[k][segments + 1][4] int32 =
+ * round(1024 (Cx, Cy, W Nx, W Ny)): the centre line resampled at equal arclength, W the largest chain distance, N the unit
+ * normal (-Ty, Tx); with half = 0 the knots start at the end with the smaller x (y, if the line is taller than wide).
+ * valid[k] = 0 and zero knots: a centre line of no length, W = 0, no area, or a value beyond int32.  ends[k][2] = (i, j) as
+ * found, info[k][3] = {E, W, length of the centre line}.  segments 4 .. 64; 1 for any argument outside its range. */
+int dbn_polygon_ribbons(const double* xy, const long long* offs, int K, int segments, int half, int threads, int* knots,
+                        unsigned char* valid, int* ends, double* info);
+/* K crops into dst[K][out_h][out_w][3] uint8 (every byte written; dst_bytes >= K * out_h * out_w * 3), one launch (none
+ * for K = 0): crop q samples the uint8 HWC image desc[q][3] int64 = {byte offset in src, height, width} along the ribbon
+ * knots[q][segments + 1][4] (dbn_polygon_ribbons' layout; any int32 values).  Pixel (x, y): k = x segments div out_w, r = x
+ * segments mod out_w, c = out_w c_k + r (c_k+1 - c_k), n likewise, P = floor((2 out_h c + (2 y - out_h) n + out_h out_w) /
+ * (2 out_h out_w)) per axis in 64-bit integers, P5 = (P + 16) >> 5, tap P5 >> 5 with the weights (32 - f | f), f = P5 & 31,
+ * of the 2 x 2 taps (outside the image: 0), (sum + 512) >> 10.  valid[q] = 0, or a descriptor that leaves src_bytes or
+ * 1 .. 65535 a side, gives a zero crop.  Sides <= 65535 and out_h * out_w <= 2^30, which keeps every term below 2^63. */
+int dbn_rectify_u8(const unsigned char* src, long src_bytes, const long long* desc, const int* knots, const unsigned char* valid, int K,
+                   int segments, int out_h, int out_w, unsigned char* dst, long dst_bytes, void* stream);
+
 /* ---- showing a detection result: utils.draw_bbox + the heat-map overlay of utils.visualize_polygon / visualize_heatmap
  *      (utils.py:110-113,202-283; csrc/render.hip, db_text_minimal_amd/render.py).  Thick strokes are this project's
  *      definition, the resize is PARITY UNPINNED against cv2. ---- */
