@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// The public C ABI: every unit sees the declarations, so a definition that disagrees with the header does not compile.
+#include "../../include/dbnet_hip.h"
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -122,9 +125,7 @@ __device__ __forceinline__ float dbn_affine_relu(float y, float sc, float sh) { 
 // AT = 0: fp32 (BASELINE configs[1]), 1: bf16 (configs[2]/[3]: bf16 activations, gradients and weight panels in HBM; fp32
 // accumulators, BatchNorm statistics, loss sums, master weights), 2: fp16 (configs[4]: inference).  Every kernel computes
 // in fp32 registers; only what crosses HBM changes.  Helpers move FOUR consecutive elements (16 B fp32 / 8 B 16-bit).
-#define DBN_AT_F32 0
-#define DBN_AT_BF16 1
-#define DBN_AT_F16 2
+// (DBN_AT_F32 / DBN_AT_BF16 / DBN_AT_F16: include/dbnet_hip.h)
 typedef unsigned dbn_u32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 dbn_f16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 dbn_bf16x2 __attribute__((ext_vector_type(2)));

@@ -6,7 +6,6 @@
 // modules/basic.py:32-36, modules/segmentation_body.py:64-77 and modules/segmentation_head.py:24-29,64-79
 // (Conv2d / ConvTranspose2d forward and their data gradients).
 #include "igemm_common.h"
-#include "../../include/dbnet_hip.h"
 
 long dbn_g_pixel_limit = 1L << 24;
 long dbn_g_byte_limit = 0xF0000000L;

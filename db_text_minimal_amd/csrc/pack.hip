@@ -117,11 +117,8 @@ __global__ void pack_weights_bf16s_kernel(const float* __restrict__ w, int O, in
 
 // ---- all weight panels of a model in ONE launch (after every optimizer step every panel is stale) ----
 // job = one dbn_pack_weights call; blockIdx.y = job, the job's parity classes are walked inside.
-struct PackJob {
-    const float* w;
-    void* out;
-    int O, I, R, S, mode, Cs, Cd, f;
-};
+using PackJob = dbn_pack_job;  // include/dbnet_hip.h
+static_assert(sizeof(PackJob) == 48, "dbn_pack_job is 48 bytes in the ABI");
 
 // workgroups per job (grid-stride inside; those past a job's size leave at once).  48 until late in round 5: the model's largest jobs
 // (512 x 512 x 9) then walked 24 groups of scattered loads per thread, the launch took 256 us in bf16 — on the second stream, but beside the

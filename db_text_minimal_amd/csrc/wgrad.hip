@@ -133,13 +133,8 @@ __global__ __launch_bounds__(1024) void wgrad_reduce64_kernel(const float* __res
 // small reduction behind every weight-gradient kernel — 34 launches of 5-40 us that each hold the stream's next matrix kernel back
 // until their last workgroup has drained (0.46 ms of work, 4.6 ms in flight at bs16 640^2).  Workgroup b looks its job up in the
 // prefix table `first` (jobs' first workgroup; n_jobs + 1 entries) and runs wgrad_reduce64_kernel's body on it: same sums, same order.
-struct WgradReduceJob {  // == dbn_wgrad_reduce_job (include/dbnet_hip.h)
-    const float* slab;
-    float* grad;
-    int splitk, O, J, Jp, BM, BN, Cb, I, RS, G, natural, blocks;
-    float scale;
-    int smem_bytes;
-};
+using WgradReduceJob = dbn_wgrad_reduce_job;  // include/dbnet_hip.h
+static_assert(sizeof(WgradReduceJob) == 72, "dbn_wgrad_reduce_job is 72 bytes in the ABI");
 __global__ __launch_bounds__(1024) void wgrad_reduce64_many_kernel(const WgradReduceJob* __restrict__ jobs, const int* __restrict__ first,
                                                                    int n_jobs) {
     extern __shared__ double dsm[];

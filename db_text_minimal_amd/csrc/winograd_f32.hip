@@ -771,11 +771,8 @@ __global__ void winograd_pack_kernel(const float* __restrict__ w, int O, int I, 
 }
 
 // every panel of a model in one launch: blockIdx.y = job
-struct WinoPackJob {
-    const float* w;
-    float* out;
-    int O, I, Cs, dgrad;
-};
+using WinoPackJob = dbn_winograd_pack_job;  // include/dbnet_hip.h
+static_assert(sizeof(WinoPackJob) == 32, "dbn_winograd_pack_job is 32 bytes in the ABI");
 // workgroups per job: FEW on purpose — the launch runs on the second stream beside the fp32 stem conv and ends long before the first
 // Winograd conv needs a panel; wider grids finish sooner and slow the stem more — the opposite
 // of pack_many_kernel in the 16-bit modes (pack.hip)

@@ -50,10 +50,14 @@ int dbn_igemm_f32(const float* src, const float* wpk, const float* bias, float* 
  * "bf16 compute").  Panels must come from dbn_pack_weights_bf16s with the same (mode, stride, ns). */
 int dbn_pack_weights_bf16s(const float* w_oihw, int O, int I, int R, int S, int mode, int stride, int ns, float* out, void* stream);
 /* All weight panels of a model in one launch (after an optimizer step every panel is stale: ~80 dbn_pack_weights calls of a
- * few microseconds each otherwise).  jobs: DEVICE array of n records
- *   struct { const float* w; void* out; int O, I, R, S, mode, Cs, Cd, f; }   (48 bytes)
+ * few microseconds each otherwise).  jobs: DEVICE array of n dbn_pack_job records (48 bytes each)
  * with Cs = (mode 0 ? I rounded up to 4 : O), Cd = (mode 0 ? O : I), f = (mode 1 && stride > 1 ? stride : 1);
  * out sized by dbn_igemm_panel_floats / dbn_igemm_bf16s_panel_floats.  ns = 0: fp32 panels; 1, 3: split-bf16 panels. */
+typedef struct dbn_pack_job {
+    const float* w;
+    void* out;
+    int O, I, R, S, mode, Cs, Cd, f;
+} dbn_pack_job;
 int dbn_pack_weights_batched(const void* jobs, int n, int ns, void* stream);
 long dbn_igemm_bf16s_panel_floats(int O, int I, int R, int S, int mode, int stride, int ns);
 int dbn_igemm_bf16s(const float* src, const float* wpk, const float* bias, float* dst, int N, int Hs, int Ws, int Cs, int Hd,
@@ -280,8 +284,13 @@ long dbn_winograd_panel_floats(int O, int Cs);
 /* dgrad = 0: panel of the forward conv of w [O][I][3][3] over a source with Cs >= I channels.  dgrad = 1: panel of the DATA GRADIENT
  * of the conv with weights w [I][O][3][3] (filters rotated by 180 degrees, channel roles swapped): maps dy (Cs >= I channels) to dx (O). */
 int dbn_winograd_pack(const float* w_oihw, int O, int I, int Cs, int dgrad, float* out, void* stream);
-/* n dbn_winograd_pack calls in one launch (after an optimizer step every panel is stale).  jobs: DEVICE array of n records
- *   struct { const float* w; float* out; int O, I, Cs, dgrad; }   (32 bytes) */
+/* n dbn_winograd_pack calls in one launch (after an optimizer step every panel is stale).  jobs: DEVICE array of n
+ * dbn_winograd_pack_job records (32 bytes each) */
+typedef struct dbn_winograd_pack_job {
+    const float* w;
+    float* out;
+    int O, I, Cs, dgrad;
+} dbn_winograd_pack_job;
 int dbn_winograd_pack_batched(const void* jobs, int n, void* stream);
 int dbn_winograd_rows(int N, int H, int W);
 /* The data gradient through the same kernel: dx [N,H,W,Cd] = [dx +] conv(dy [N,H,W,Cs]) with the dgrad = 1 panel.  y non-NULL: the

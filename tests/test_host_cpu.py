@@ -3,6 +3,8 @@
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 import sys
 
 import pytest
@@ -34,15 +36,122 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
         assert hasattr(lib, name)
 
 
-def test_ctypes_signatures_match_header():
-    for name, args in header_decls():
-        kinds = ''
-        args = args.strip()
-        if args and args != 'void':
-            for a in args.split(','):
-                a = a.strip()
-                kinds += 'p' if '*' in a else 'l' if a.startswith('long') else 'f' if a.startswith('float') else 'd' if a.startswith('double') else 'i'
+def test_every_defined_dbn_symbol_is_declared_in_the_header():
+    """The reverse direction: an extern "C" dbn_* function that the library defines and the header does not declare
+    would be an entry point no compiler compares with anything."""
+    out = subprocess.run(['nm', '-D', '--defined-only', _lib.build()], capture_output=True, text=True, check=True).stdout
+    defined = {f[2] for f in map(str.split, out.splitlines()) if len(f) == 3 and f[1] in 'TtWw' and f[2].startswith('dbn_')}
+    assert len(defined) >= 200, len(defined)
+    assert not defined - set(_lib.SIGNATURES), sorted(defined - set(_lib.SIGNATURES))
+
+
+# one declaration per type spelling of include/dbnet_hip.h, in the forms the header writes them
+PARSER_TEXT = """
+/* a comment that holds a declaration:  int dbn_in_a_comment(short x);  and spans
+ * two lines */
+#ifndef SOME_GUARD_H
+#define SOME_GUARD_H
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define DBN_SOME_CONSTANT 3
+typedef struct dbn_rec {
+    int* counters;
+    float *a, *b;  // two pointers from one base type
+    const float* w;
+    void* out;
+    int O, I;
+    float scale;
+} dbn_rec;
+int dbn_none(void);
+long dbn_empty();
+int dbn_values(int a, long b, float c, double d);
+long dbn_broken(const double* a, double* b,
+                const float* c,
+                float* d, const int* e, int* f);
+int dbn_ints(const long long* a, long long* b, unsigned long long* c, const short* d, short* e, const unsigned short* f,
+             unsigned short* g, const unsigned* h, unsigned* i);
+int dbn_bytes(const unsigned char* a, unsigned char* b, const void* c, void* d, const dbn_bnb_final* fin);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+PARSER_SPELLINGS = {'int', 'long', 'float', 'double', 'const double*', 'double*', 'const float*', 'float*', 'const int*', 'int*',
+                    'const long long*', 'long long*', 'unsigned long long*', 'const short*', 'short*', 'const unsigned short*',
+                    'unsigned short*', 'const unsigned*', 'unsigned*', 'const unsigned char*', 'unsigned char*', 'const void*', 'void*',
+                    'const dbn_bnb_final*'}
+
+
+def test_header_parser_on_literal_text():
+    sigs, longs, records, spellings = _lib.parse_header(PARSER_TEXT)
+    assert sigs == {'dbn_none': '', 'dbn_empty': '', 'dbn_values': 'ilfd', 'dbn_broken': 'pppppp', 'dbn_ints': 'ppppppppp',
+                    'dbn_bytes': 'ppppp'}
+    assert longs == {'dbn_empty', 'dbn_broken'}
+    assert records == {'dbn_rec': [('counters', 'p'), ('a', 'p'), ('b', 'p'), ('w', 'p'), ('out', 'p'), ('O', 'i'), ('I', 'i'),
+                                   ('scale', 'f')]}
+    assert spellings == PARSER_SPELLINGS and len(PARSER_SPELLINGS) == 24
+    # ... and these are the spellings of the real header: a new one there needs a declaration above
+    assert _lib.parse_header(open(_lib.HEADER).read())[3] == PARSER_SPELLINGS
+
+
+@pytest.mark.parametrize('decl', ['int dbn_f(int a, short n);', 'int dbn_f(unsigned n);', 'int dbn_f(size_t n, void* p);',  # unknown by value
+                                  'int dbn_f(int);', 'int dbn_f(int a[4]);', 'void dbn_f(int a);', 'int dbn_f(int a) { return a; }',
+                                  'typedef struct dbn_r { short n; } dbn_r;', 'typedef struct dbn_r { int n; } dbn_s;'])
+def test_header_parser_refuses_what_it_does_not_know(decl):
+    with pytest.raises(_lib.HipLibraryError, match='dbn_f|dbn_r'):
+        _lib.parse_header('int dbn_before(int a);\n' + decl + '\nint dbn_after(void);\n')
+
+
+def test_missing_header_fails_loudly(monkeypatch, tmp_path):
+    monkeypatch.setattr(_lib, 'HEADER', str(tmp_path / 'include' / 'dbnet_hip.h'))
+    with pytest.raises(_lib.HipLibraryError, match=re.escape(str(tmp_path / 'include' / 'dbnet_hip.h'))):
+        _lib._read_header()
+
+
+def test_real_entries_against_hand_written_expectations():
+    """Frozen copies of six rows of the hand-written table this module held before the header became the one declaration,
+    and the sizes of the four records."""
+    frozen = {'dbn_head_tail_bn_bwd_t': 'ii' + 'p' * 28 + 'iiii' + 'ff' + 'pp',
+              'dbn_db_loss_fwd': 'pp' + 'iiii' + 'ffdf' + 'pppp',
+              'dbn_jpeg_dhuff_ws_bytes': 'l',
+              'dbn_adam_step': 'pppp' + 'l' + 'ffff' + 'i' + 'f' + 'p',
+              'dbn_rectify_u8': 'plpppiiiiplp',
+              'dbn_head_tail_bwd_ws_floats': ''}
+    for name, kinds in frozen.items():
         assert _lib.SIGNATURES[name] == kinds, name
+    assert {n for n in frozen if n in _lib.LONG_RETURN} == {'dbn_jpeg_dhuff_ws_bytes'}
+    assert [ctypes.sizeof(r) for r in (_lib.WgradReduceJob, _lib.PackJob, _lib.WinogradPackJob, _lib.BnbFinal)] == [72, 48, 32, 72]
+    assert [f for f, _ in _lib.PackJob._fields_] == ['w', 'out', 'O', 'I', 'R', 'S', 'mode', 'Cs', 'Cd', 'f']
+    L = _lib.lib()
+    assert L.dbn_jpeg_dhuff_ws_bytes.restype is ctypes.c_long and L.dbn_adam_step.restype is ctypes.c_int
+    assert L.dbn_db_loss_fwd.argtypes[8] is ctypes.c_double and L.dbn_adam_step.argtypes[4] is ctypes.c_long
+
+
+def test_compiler_compares_the_header_with_the_definitions(tmp_path):
+    """csrc/common.h includes the header, so a definition that disagrees with its declaration does not compile: a copy of
+    one small unit passes the host syntax check as it is and stops with `conflicting types` once one parameter type of a
+    function it defines is changed in the copied header."""
+    csrc = tmp_path / 'db_text_minimal_amd' / 'csrc'
+    csrc.mkdir(parents=True)
+    for f in ('mfma_probe.hip', 'common.h'):
+        shutil.copy(os.path.join(_lib.CSRC, f), csrc)
+    shutil.copytree(os.path.join(ROOT, 'include'), tmp_path / 'include')
+    make = open(os.path.join(_lib.CSRC, 'Makefile')).read()
+    hipcc, std = re.search(r'^HIPCC \?= (\S+)', make, re.M).group(1), re.search(r'-std=\S+', make).group(0)
+
+    def syntax_check():
+        return subprocess.run([hipcc, '--cuda-host-only', '-fsyntax-only', std, 'mfma_probe.hip'], cwd=csrc, capture_output=True, text=True)
+
+    res = syntax_check()
+    assert res.returncode == 0, res.stderr[-2000:]
+    hdr = tmp_path / 'include' / 'dbnet_hip.h'
+    text = hdr.read_text()
+    decl = 'long dbn_mfma_sustained_flops(int kind, int iters);'
+    assert text.count(decl) == 1
+    hdr.write_text(text.replace(decl, 'long dbn_mfma_sustained_flops(int kind, long iters);'))
+    res = syntax_check()
+    assert res.returncode != 0 and "conflicting types for 'dbn_mfma_sustained_flops'" in res.stderr, res.stderr[-2000:]
 
 
 def test_size_queries_without_gpu():

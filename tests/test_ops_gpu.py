@@ -1023,10 +1023,7 @@ def test_batched_weight_pack_equals_single_packs(ns):
     import ctypes
     jobs_spec = [((64, 3, 7, 7), 0, 2), ((128, 64, 3, 3), 0, 1), ((128, 64, 3, 3), 1, 2), ((64, 256, 10, 10), 1, 8), ((64, 64, 2, 2), 1, 2),
                  ((256, 128, 1, 1), 1, 1), ((64, 256, 6, 6), 1, 4)]
-
-    class Job(ctypes.Structure):
-        _fields_ = [('w', ctypes.c_void_p), ('out', ctypes.c_void_p)] + [(f, ctypes.c_int) for f in ('O', 'I', 'R', 'S', 'mode', 'Cs', 'Cd', 'f')]
-
+    Job = _lib.PackJob
     ws, singles, outs = [], [], []
     arr = (Job * len(jobs_spec))()
     for i, (shape, mode, stride) in enumerate(jobs_spec):
