@@ -8,7 +8,8 @@ from .gt_maps import gt_collate, make_gt_maps, normalize_images, offset_polygon 
 from .postprocess import SegDetectorRepresenter, detect_boxes, detect_polygons  # noqa: F401
 from .det_eval import DetectionDetEvalEvaluator, DetectionIoUEvaluator, QuadMetric, polygon_overlaps  # noqa: F401
 from .augment import DeviceBatches, augment_images, image_collate, plan_augment, plan_letterbox, preprocess_image  # noqa: F401
-from .word_crops import crop_words, perspective_maps, polygon_ribbons, rectify_from_ribbons, rectify_words  # noqa: F401
+from .word_crops import (crop_words, perspective_maps, polygon_ribbons, polygon_ribbons_device, rectify_from_ribbons,  # noqa: F401
+                         rectify_words)
 from .render import draw_outlines, image_views, minmax_scale_u8, overlay_heatmap, render_detections  # noqa: F401
 from .render import draw_dots, draw_labels, draw_scores, draw_words, text_size  # noqa: F401
 from .recognise import AttnLabelConverter, CTCLabelConverter, greedy_decode, recognize_words, words_to_input  # noqa: F401

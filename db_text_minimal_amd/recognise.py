@@ -174,11 +174,11 @@ def _box_rows(boxes):
 
 
 def recognize_words(images, boxes, model, converter, prediction='CTC', batch_size=512, batch_max_length=25, rgb=False, size=SIZE,
-                    scores=None, min_score=None, polygons=None, segments=32, ends='auto'):
+                    scores=None, min_score=None, polygons=None, segments=32, ends='auto', ribbons='host'):
     """From images and detected boxes to strings: crop_words -> words_to_input -> model -> greedy_decode -> converter.decode.
 
     images, boxes, size, scores, min_score: as crop_words takes them.  Or polygons= (with boxes = None) instead of boxes:
-    images, polygons, size, scores, min_score, segments, ends as rectify_words takes them, which then cuts the crops.  Or
+    images, polygons, size, scores, min_score, segments, ends, ribbons as rectify_words takes them, which then cuts the crops.  Or
     ready crops: images = a uint8 device tensor [K, h, w, 3] with boxes = None.
     model: the user's recogniser, called under no_grad in chunks of batch_size as the reference calls it, with text_for_pred a zero LongTensor [b, batch_max_length + 1]: model(image, text_for_pred) for
     prediction 'CTC', model(image, text_for_pred, is_train=False) for 'Attn'; it returns logits [b, T, C].
@@ -187,6 +187,8 @@ def recognize_words(images, boxes, model, converter, prediction='CTC', batch_siz
     all words."""
     if boxes is not None and polygons is not None:
         raise ValueError('boxes or polygons, not both')
+    if not (isinstance(ribbons, str) and ribbons in ('host', 'device')):
+        raise ValueError("ribbons must be 'host' or 'device', got %r" % (ribbons, ))
     if 'CTC' in prediction:
         mode = 'ctc'
     elif 'Attn' in prediction:
@@ -198,7 +200,7 @@ def recognize_words(images, boxes, model, converter, prediction='CTC', batch_siz
         raise ValueError('batch_size must be positive')
     if polygons is not None:
         polygons = list(polygons)
-        crops, index = rectify_words(images, polygons, size, scores, min_score, segments, ends)
+        crops, index = rectify_words(images, polygons, size, scores, min_score, segments, ends, ribbons=ribbons)
         rows = [[np.asarray(p) for p in (ps[0] if isinstance(ps, tuple) and len(ps) == 2 else ps)] for ps in polygons]
         n_images = 1 if isinstance(images, torch.Tensor) else len(images[1])
     elif boxes is None:

@@ -17,6 +17,8 @@ The reference stops there (test_ocr.py:162 crops only `if not opt.is_output_poly
 
   polygon_ribbons(polygons, segments, ends)          host: the ribbon of every polygon (centre line and cross-sections,
                                                      fp64 -> int32 units of 1 / 1024 px), one C call
+  polygon_ribbons_device(polygons, segments, ends)   device: the same ribbons with the same bits, one launch (csrc/rectify.hip
+                                                     polygon_ribbons_kernel); rectify_words(..., ribbons='device') uses it
   rectify_words(images, polygons, size, ...)         device: every kept polygon straightened into an h x w crop, one launch
                                                      (csrc/rectify.hip rectify_u8), and their (image, polygon row) index
   rectify_from_ribbons(images, knots, valid, ...)    the device half alone, on knots of the caller's choosing
@@ -213,6 +215,50 @@ def polygon_ribbons(polygons, segments=32, ends='auto', return_info=False):
     return knots, valid
 
 
+def _checked_vertices(polygons, ends):
+    """_polygon's checks for a whole batch -> (vertex counts, fp64 [total, 2]): shapes and counts per polygon, the values
+    once on the concatenated vertices (a batch waits for these checks longer than for the kernel); anything out of order
+    goes through _polygon one by one, which raises what polygon_ribbons raises"""
+    arrs = [np.asarray(p) for p in polygons]
+    if arrs and all(a.ndim == 2 and a.shape[1] == 2 and a.dtype.kind in 'iuf' and 3 <= a.shape[0] <= _MAX_VERTS and
+                    not (ends == 'half' and a.shape[0] % 2) for a in arrs):
+        xy = np.concatenate(arrs).astype(np.float64, copy=False)
+        if (np.abs(xy) <= _MAX_COORD).all():
+            return [a.shape[0] for a in arrs], xy
+    polys = [_polygon(p, ends) for p in arrs]
+    return [len(p) for p in polys], (np.concatenate(polys) if polys else np.zeros((0, 2), np.float64))
+
+
+def polygon_ribbons_device(polygons, segments=32, ends='auto', return_info=False, device=None):
+    """polygon_ribbons on the device (dbn_polygon_ribbons_device, one workgroup per polygon): the same
+    arguments, the same ValueErrors before any work, and the same bits, as torch tensors on the device: (knots int32
+    [K, S + 1, 4], valid uint8 [K])[, and with return_info a dict of device tensors: ends int32 [K, 2], E, width, length
+    fp64 [K]].  One pinned, non-blocking copy of the vertices and their offsets, one launch on the current stream, no
+    synchronisation; K = 0: empty tensors, no launch."""
+    S = _segments(segments)
+    if ends not in ('auto', 'half'):
+        raise ValueError("ends must be 'auto' or 'half', got %r" % (ends, ))
+    counts, xy = _checked_vertices(polygons, ends)
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    if dev.type != 'cuda':
+        raise ValueError('polygon_ribbons_device runs on a GPU device, not %s' % dev)
+    K = len(counts)
+    knots, valid = torch.empty((K, S + 1, 4), device=dev, dtype=torch.int32), torch.empty(K, device=dev, dtype=torch.uint8)
+    found, info = torch.empty((K, 2), device=dev, dtype=torch.int32), torch.empty((K, 3), device=dev, dtype=torch.float64)
+    if K:
+        offs = _offsets(counts)
+        total = int(offs[-1])
+        both = np.empty(K + 1 + 2 * total, np.float64)  # the K + 1 offsets (as int64) and the vertices behind them: one copy
+        both[:K + 1].view(np.int64)[:] = offs
+        both[K + 1:] = xy.reshape(-1)
+        d = _to_device(both, dev)
+        check(lib().dbn_polygon_ribbons_device(d.data_ptr() + 8 * (K + 1), d.data_ptr(), K, total, S, int(ends == 'half'), knots.data_ptr(),
+                                               valid.data_ptr(), found.data_ptr(), info.data_ptr(), _stream(dev)), 'polygon_ribbons_device')
+    if return_info:
+        return knots, valid, dict(ends=found, E=info[:, 0].contiguous(), width=info[:, 1].contiguous(), length=info[:, 2].contiguous())
+    return knots, valid
+
+
 def select_polygons(polygons, scores=None, min_score=None):
     """The polygons rectify_words straightens: per image a list of [P, 2] arrays (or the (polygons, scores) pairs of
     detect_polygons), those with a coordinate sum <= 0 dropped and, with min_score, those scoring below it: select_boxes'
@@ -247,14 +293,22 @@ def select_polygons(polygons, scores=None, min_score=None):
 def rectify_from_ribbons(images, knots, valid, image_index, size=SIZE, device=None):
     """The device half of rectify_words alone (dbn_rectify_u8, one launch): crop q is read from image image_index[q] along
     the ribbon knots[q] (int32 [S + 1, 4], polygon_ribbons' layout, any values); valid[q] = 0 gives a zero crop.  images as
-    crop_words takes them.  -> uint8 [K, h, w, 3] on the device."""
+    crop_words takes them.  knots and valid are numpy arrays, or both CUDA tensors (int32 / uint8, contiguous, on the
+    device that cuts the crops, as polygon_ribbons_device returns them), which are used in place.  -> uint8 [K, h, w, 3]
+    on the device."""
     h, w = _size(size)
     packed, shapes = _images(images)
-    knots = np.ascontiguousarray(knots, dtype=np.int32)
+    on_device = isinstance(knots, torch.Tensor) or isinstance(valid, torch.Tensor)
+    if on_device:  # polygon_ribbons_device's tensors, used where they are
+        for name, a, dtype in (('knots', knots, torch.int32), ('valid', valid, torch.uint8)):
+            if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == dtype and a.is_contiguous()):
+                raise ValueError('%s on the device must be a contiguous %s CUDA tensor (and so must the other)' % (name, dtype))
+    else:
+        knots = np.ascontiguousarray(knots, dtype=np.int32)
     if knots.ndim != 3 or knots.shape[2] != 4:
-        raise ValueError('knots must be int32 [K, S + 1, 4], got shape %s' % (knots.shape, ))
+        raise ValueError('knots must be int32 [K, S + 1, 4], got shape %s' % (tuple(knots.shape), ))
     K, S = knots.shape[0], _segments(knots.shape[1] - 1)
-    valid = np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)
+    valid = valid.reshape(-1) if on_device else np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)
     image_index = np.ascontiguousarray(image_index, dtype=np.int64).reshape(-1)
     if valid.shape[0] != K or image_index.shape[0] != K:
         raise ValueError('%d ribbons, %d valid flags, %d image indices' % (K, valid.shape[0], image_index.shape[0]))
@@ -266,6 +320,8 @@ def rectify_from_ribbons(images, knots, valid, image_index, size=SIZE, device=No
     dev = torch.device(device) if device is not None else (packed.device if packed.is_cuda else torch.device('cuda', torch.cuda.current_device()))
     if dev.type != 'cuda':
         raise ValueError('rectify_words runs on a GPU device, not %s' % dev)
+    if on_device and {knots.device.index, valid.device.index} != {torch.cuda.current_device() if dev.index is None else dev.index}:
+        raise ValueError('knots on %s and valid on %s, the crops are cut on %s' % (knots.device, valid.device, dev))
     src = _packed(packed, shapes, dev)
     crops = torch.empty((K, h, w, 3), device=dev, dtype=torch.uint8)
     if K == 0:
@@ -273,13 +329,14 @@ def rectify_from_ribbons(images, knots, valid, image_index, size=SIZE, device=No
     src_off = _offsets([sh * sw * 3 for sh, sw in shapes])
     hw = np.array(shapes, np.int64)[image_index]
     desc = np.stack([src_off[image_index], hw[:, 0], hw[:, 1]], 1)
-    d, kn, va = _to_device(desc, dev), _to_device(knots, dev), _to_device(valid, dev)
+    d = _to_device(desc, dev)
+    kn, va = (knots, valid) if on_device else (_to_device(knots, dev), _to_device(valid, dev))
     check(lib().dbn_rectify_u8(src.data_ptr(), src.numel(), d.data_ptr(), kn.data_ptr(), va.data_ptr(), K, S, h, w, crops.data_ptr(),
                                crops.numel(), _stream(dev)), 'rectify_u8')
     return crops
 
 
-def rectify_words(images, polygons, size=SIZE, scores=None, min_score=None, segments=32, ends='auto', device=None):
+def rectify_words(images, polygons, size=SIZE, scores=None, min_score=None, segments=32, ends='auto', device=None, ribbons='host'):
     """Every kept text polygon of every image straightened into an h x w word image, on the device: crop_words for curved
     text.  The reference crops boxes only (test_ocr.py:162), so what a straightened polygon is is this project's
     definition: the ribbon of polygon_ribbons, sampled with x = 0 on its start cap and y = 0 on its top
@@ -289,11 +346,19 @@ def rectify_words(images, polygons, size=SIZE, scores=None, min_score=None, segm
     images: as crop_words takes them.  polygons: per image a list of [P, 2] arrays in the images' pixel coordinates, or
     the (polygons, scores) pairs of detect_polygons(..., dest_sizes=...).  Dropped: polygons whose coordinates sum to <= 0
     and, with min_score, those scoring below it.  Returns (crops, index): crops uint8 [K, h, w, 3] on the device, index
-    int64 [K, 2] numpy of (image, polygon row).  One host call for the ribbons, one launch on the current stream."""
+    int64 [K, 2] numpy of (image, polygon row).  One host call for the ribbons, one launch on the current stream; with
+    ribbons='device' the ribbons are found on the device too (polygon_ribbons_device: the same knots, so the same bytes)
+    and stay there: the vertices cross to the device, no knots."""
     _size(size)
+    if not (isinstance(ribbons, str) and ribbons in ('host', 'device')):
+        raise ValueError("ribbons must be 'host' or 'device', got %r" % (ribbons, ))
     packed, shapes = _images(images)
     kept, index = select_polygons(polygons, scores, min_score)
     if index.size and int(index[:, 0].max()) >= len(shapes):
         raise ValueError('polygons for %d images, but %d images' % (int(index[:, 0].max()) + 1, len(shapes)))
-    knots, valid = polygon_ribbons(kept, segments, ends)
+    if ribbons == 'device':
+        # where rectify_from_ribbons will cut them: the packed images' device, else the current one
+        knots, valid = polygon_ribbons_device(kept, segments, ends, device=device if device is not None or not packed.is_cuda else packed.device)
+    else:
+        knots, valid = polygon_ribbons(kept, segments, ends)
     return rectify_from_ribbons((packed, shapes), knots, valid, index[:, 0], size, device), index

@@ -478,6 +478,14 @@ int dbn_warp_perspective_u8(const unsigned char* src, long src_bytes, const long
  * found, info[k][3] = {E, W, length of the centre line}.  segments 4 .. 64; 1 for any argument outside its range. */
 int dbn_polygon_ribbons(const double* xy, const long long* offs, int K, int segments, int half, int threads, int* knots,
                         unsigned char* valid, int* ends, double* info);
+/* device: the same ribbons with the same bits, one launch (none for K = 0), one workgroup per polygon.  All
+ * pointers are device pointers with dbn_polygon_ribbons' layouts; xy holds total_vertices vertices.  The call checks K,
+ * segments, half, total_vertices >= 0 and the pointers; the kernel checks what they hold: a polygon with offs[k] < 0,
+ * offs[k + 1] > total_vertices, a vertex count outside 3 .. 256 (odd with half = 1) or a coordinate that is not within
+ * +-2^20 gets valid 0, zero knots, ends (-1, -1) and info 0, and nothing outside xy is read.  Every output byte of every
+ * polygon is written. */
+int dbn_polygon_ribbons_device(const double* xy, const long long* offs, int K, long total_vertices, int segments, int half, int* knots,
+                               unsigned char* valid, int* ends, double* info, void* stream);
 /* K crops into dst[K][out_h][out_w][3] uint8 (every byte written; dst_bytes >= K * out_h * out_w * 3), one launch (none
  * for K = 0): crop q samples the uint8 HWC image desc[q][3] int64 = {byte offset in src, height, width} along the ribbon
  * knots[q][segments + 1][4] (dbn_polygon_ribbons' layout; any int32 values).  Pixel (x, y): k = x segments div out_w, r = x

@@ -6,12 +6,16 @@ vertices (10 a side, as an unclipped detection or a Total-Text annotation has th
 Prints:
   host     polygon_ribbons for the batch (dbn_polygon_ribbons, one call, up to 16 threads), ends='auto' (the search) and
            ends='half' (no search), median
+  ribbons  dbn_polygon_ribbons_device alone (vertices and offsets already on the device), both ends, the same way as the
+           launches below, and its knots, valid flags, ends and info against the host's: equal or not
+  largest  one polygon of 256 vertices at 64 segments, device launch and host call: one workgroup owns a polygon, so this is
+           the latency floor of the kernel's shape
   device   dbn_rectify_u8 alone (descriptors and knots already on the device), median of timed launches after warm-up
            (device events), against its byte floor at 8 TB/s: the crops written plus the source bytes inside the polygons
            (their shoelace areas, 3 bytes per pixel)
   boxes    dbn_warp_perspective_u8 alone on the same number of boxes (each polygon's end-to-end rectangle), the same way
-  e2e      rectify_words from a device batch: selection, the ribbons call, the copies and the launch, wall clock to a
-           synchronised device, median
+  e2e      rectify_words from a device batch: selection, the ribbons (ribbons='host' and ribbons='device'), the copies and
+           the launch, wall clock to a synchronised device, median; and whether both gave the same crops
   check    device == the numpy restatement tests/rectify_ref.py on the crops it samples
 Usage: python tools/rectify_probe.py [--reps 50] [--out file]
 """
@@ -28,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
-from db_text_minimal_amd import perspective_maps, polygon_ribbons, rectify_words  # noqa: E402
+from db_text_minimal_amd import perspective_maps, polygon_ribbons, polygon_ribbons_device, rectify_words  # noqa: E402
 from db_text_minimal_amd import word_crops as Wc  # noqa: E402
 from db_text_minimal_amd._lib import check, lib  # noqa: E402
 import rectify_ref as R  # noqa: E402
@@ -63,6 +67,29 @@ def polygons_for(rng):
 def shoelace(p):
     x, y = p[:, 0].astype(np.float64), p[:, 1].astype(np.float64)
     return 0.5 * abs((x * np.roll(y, -1) - np.roll(x, -1) * y).sum())
+
+
+def time_device_ribbons(L, polys, S, half, dev, stream, reps):
+    """dbn_polygon_ribbons_device alone on polygons already on the device -> (median ms, its outputs on the host)"""
+    K = len(polys)
+    xy = torch.from_numpy(np.concatenate(polys).astype(np.float64)).to(dev)
+    offs = torch.from_numpy(Wc._offsets([len(p) for p in polys])).to(dev)
+    knots, valid = torch.empty((K, S + 1, 4), device=dev, dtype=torch.int32), torch.empty(K, device=dev, dtype=torch.uint8)
+    found, info = torch.empty((K, 2), device=dev, dtype=torch.int32), torch.empty((K, 3), device=dev, dtype=torch.float64)
+
+    def launch():
+        check(L.dbn_polygon_ribbons_device(xy.data_ptr(), offs.data_ptr(), K, xy.shape[0], S, half, knots.data_ptr(), valid.data_ptr(),
+                                           found.data_ptr(), info.data_ptr(), stream), 'polygon_ribbons_device')
+
+    t = time_launch(launch, reps)
+    return t, (knots.cpu().numpy(), valid.cpu().numpy(), found.cpu().numpy(), info.cpu().numpy())
+
+
+def same_ribbons(got, polys, S, ends):
+    knots, valid, info = polygon_ribbons(polys, S, ends, return_info=True)
+    want = (knots, valid, info['ends'], np.stack([info['E'], info['width'], info['length']], 1))
+    return all(np.array_equal(g.view(np.int64) if g.dtype == np.float64 else g, w.view(np.int64) if w.dtype == np.float64 else w)
+               for g, w in zip(got, want))
 
 
 def main():
@@ -100,12 +127,24 @@ def main():
         if ends == 'auto':
             knots, valid = knots_e, valid_e
 
+    L = lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    for ends in ('auto', 'half'):
+        t, got = time_device_ribbons(L, kept, SEGMENTS, int(ends == 'half'), dev, stream, args.reps)
+        say("ribbons polygon_ribbons_device ends='%s' (measured, the launch alone): %.3f ms for %d polygons; knots, valid, ends and info %s the host's"
+            % (ends, t, K, 'EQUAL' if same_ribbons(got, kept, SEGMENTS, ends) else 'DIFFER FROM'))
+    big = [np.round(np.stack([600 + 500 * np.cos(a) * (1 + 0.1 * np.sin(5 * a)), 600 + 300 * np.sin(a)], 1) * 4) / 4
+           for a in [np.linspace(0, 2 * np.pi, 256, endpoint=False)]]
+    t, got = time_device_ribbons(L, big, 64, 0, dev, stream, max(5, args.reps // 5))
+    t0 = time.perf_counter()
+    same = same_ribbons(got, big, 64, 'auto')
+    say("largest one polygon of 256 vertices, 64 segments, ends='auto' (measured): device launch %.3f ms, host call %.1f ms (one thread, with "
+        "its early exit); %s" % (t, 1e3 * (time.perf_counter() - t0), 'EQUAL' if same else 'DIFFERENT'))
+
     off = Wc._offsets([H * W * 3] * N)
     desc = np.stack([off[index[:, 0]], np.full(K, H, np.int64), np.full(K, W, np.int64)], 1)
     d, kn, va = torch.from_numpy(desc).to(dev), torch.from_numpy(knots).to(dev), torch.from_numpy(valid).to(dev)
     crops = torch.empty((K, h, w, 3), device=dev, dtype=torch.uint8)
-    L = lib()
-    stream = torch.cuda.current_stream().cuda_stream
 
     def launch():
         check(L.dbn_rectify_u8(src.data_ptr(), src.numel(), d.data_ptr(), kn.data_ptr(), va.data_ptr(), K, SEGMENTS, h, w, crops.data_ptr(),
@@ -129,10 +168,13 @@ def main():
                                         stream), 'warp_perspective_u8')
 
     say('boxes  warp_perspective_u8 on the same count (measured) %.3f ms' % time_launch(launch_boxes, args.reps))
-    t_e2e = time_wall(lambda: rectify_words((src, shapes), polys, SIZE), max(3, args.reps // 10))
-    say('e2e    rectify_words from a device batch (measured, wall clock to a synchronised device): %.1f ms' % t_e2e)
+    for how in ('host', 'device'):
+        t_e2e = time_wall(lambda: rectify_words((src, shapes), polys, SIZE, ribbons=how), max(3, args.reps // 10))
+        say("e2e    rectify_words(ribbons='%s') from a device batch (measured, wall clock to a synchronised device): %.1f ms" % (how, t_e2e))
 
     got, _ = rectify_words((src, shapes), polys, SIZE)
+    on_device, _ = rectify_words((src, shapes), polys, SIZE, ribbons='device')
+    say("check  ribbons='device' and ribbons='host' gave %s crops (%d x %d x %d x 3 bytes)" % (('EQUAL' if torch.equal(on_device, got) else 'DIFFERENT', ) + tuple(got.shape[:3])))
     got = got.cpu().numpy()
     sample = np.linspace(0, K - 1, 40).astype(np.int64)
     for j in sample:
