@@ -147,7 +147,7 @@ def report_robust(tag, got, ref, atol, rtol, frac=0.999):
     assert f >= frac, tag
 
 
-# ---- float64 pins of the storage-typed kernels (test_train16_ops_gpu.py, test_bn_pool_ops_gpu.py) ----
+# ---- float64 pins of the storage-typed kernels (test_train16_ops_gpu.py, test_bn_pool_ops_gpu.py, test_infer16_ops_gpu.py) ----
 U = 2.0**-24
 DT = {0: torch.float32, 1: torch.bfloat16, 2: torch.float16}
 SR = {0: 2.0**-24, 1: 2.0**-8, 2: 2.0**-11}  # unit roundoff of the storage type (round to nearest even)
