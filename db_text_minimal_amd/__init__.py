@@ -16,3 +16,5 @@ from .recognise import AttnLabelConverter, CTCLabelConverter, greedy_decode, rec
 from .jpeg import (CorruptJpeg, JpegCoefficients, JpegEncodeError, JpegError, JpegStreams, UnsupportedJpeg, decode_coefficients, decode_jpeg,  # noqa: F401
                    decode_jpeg_batch, encode_jpeg, encode_jpeg_batch, entropy_decode, entropy_encode, entropy_encode_device, forward_coefficients, jpeg_collate,
                    jpeg_info, jpeg_multiscan_collate, optimal_huffman_table, quant_tables, save_jpegs, entropy_decode_device, jpeg_stream_collate, parse_streams)
+from .png import (CorruptPng, PngError, PngScanlines, UnsupportedPng, decode_image_batch, decode_png, decode_png_batch, encode_png,  # noqa: F401
+                  encode_png_batch, filter_png_rows, inflate_png, png_collate, png_info, save_pngs, unfilter_png)

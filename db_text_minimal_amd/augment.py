@@ -33,6 +33,7 @@ import torch
 from ._lib import check, lib
 from .gt_maps import GT_KEYS, MEAN, make_gt_maps, plan_polygons
 from .jpeg import JpegCoefficients, JpegStreams, decode_coefficients, entropy_decode_device, stream_orientations
+from .png import PngScanlines, unfilter_png
 
 ROTATE = (-10.0, 10.0)  # data_loaders.py:62-66
 SCALE = (0.5, 3.0)
@@ -392,7 +393,7 @@ def image_collate(items):
 
 class DeviceBatches:
     """Turns each (packed, shapes, polys, tags) batch of `loader` (collate_fn=image_collate, or jpeg_collate for JPEG bytes:
-    the first element is then a JpegCoefficients and its device half runs here) into the dict fit / evaluate consume: `img` (augment_images) and the four GT_KEYS maps (make_gt_maps), on `device`.  training=True draws the
+    the first element is then a JpegCoefficients and its device half runs here; png_collate and PngScanlines likewise) into the dict fit / evaluate consume: `img` (augment_images) and the four GT_KEYS maps (make_gt_maps), on `device`.  training=True draws the
     augmentation from np.random.RandomState(seed), continued across passes; False is the letterbox, and adds `anns`
     (per image, the scaled polygons) and `ignore_tags` (per image, the GT ignore flags) as the reference's test loader
     returns them.  orient=True: JPEG batches are decoded with their Exif orientation applied (decode_coefficients), as the
@@ -419,6 +420,8 @@ class DeviceBatches:
                     raise e
         if isinstance(packed, JpegCoefficients):  # jpeg_collate: the device half of the decode
             packed, shapes = decode_coefficients(packed, self.device, self.orient)
+        if isinstance(packed, PngScanlines):  # png_collate: the device half of the decode
+            packed, shapes = unfilter_png(packed, self.device)
         if self.training:
             plans = plan_augment(shapes, polys, self.rng, self.size)
         else:

@@ -626,6 +626,10 @@ def _is_jpeg(path):
     return path.lower().endswith(('.jpg', '.jpeg'))
 
 
+def _is_png(path):
+    return path.lower().endswith('.png')
+
+
 def _read_image(path, orient=False):
     if path.endswith('.npy'):
         img = np.load(path)
@@ -633,6 +637,10 @@ def _read_image(path, orient=False):
         from .jpeg import decode_jpeg
         with open(path, 'rb') as f:
             return decode_jpeg(f.read(), fallback=True, multiscan=True, orient=orient)
+    elif _is_png(path):  # the project's own decoder; a kind it refuses (CgBI, larger than its limits) goes through PIL when that is installed
+        from .png import decode_png
+        with open(path, 'rb') as f:
+            return decode_png(f.read(), fallback=True)
     else:
         from PIL import Image  # only when the suffix asks for it
         img = np.asarray(Image.open(path).convert('RGB'))
@@ -647,6 +655,11 @@ def _write_image(path, img):
         from .jpeg import encode_jpeg
         with open(path, 'wb') as f:
             f.write(encode_jpeg(img))
+        return
+    if _is_png(path):  # lossless, filters chosen on the GPU; PIL is not imported
+        from .png import encode_png
+        with open(path, 'wb') as f:
+            f.write(encode_png(img))
         return
     img = img.cpu().numpy()
     if path.endswith('.npy'):
@@ -663,12 +676,12 @@ def main(argv=None):
     from .models import DBTextModel
     from .postprocess import detect_boxes, detect_polygons
     ap = argparse.ArgumentParser(description='detect text in one image and draw the result (the reference\'s test.py)')
-    ap.add_argument('--image', required=True, help='.npy uint8 [H, W, 3], a .jpg / .jpeg file, or another image file when PIL is installed')
+    ap.add_argument('--image', required=True, help='.npy uint8 [H, W, 3], a .jpg / .jpeg or .png file, or another image file when PIL is installed')
     ap.add_argument('--model_path', required=True)
     ap.add_argument('--is_output_polygon', action='store_true')
     ap.add_argument('--heatmap', action='store_true', help='lay the probability map over the outlines (test.py)')
     ap.add_argument('--scores', action='store_true', help='write every detection\'s score at its first vertex (draw_scores)')
-    ap.add_argument('--out', default=None, help='.npy, .jpg / .jpeg (written by encode_jpeg), or another suffix when PIL is installed')
+    ap.add_argument('--out', default=None, help='.npy, .jpg / .jpeg (written by encode_jpeg), .png (encode_png), or another suffix when PIL is installed')
     ap.add_argument('--thresh', type=float, default=0.25)
     ap.add_argument('--box_thresh', type=float, default=0.5)
     ap.add_argument('--unclip_ratio', type=float, default=1.5)

@@ -1019,6 +1019,29 @@ int dbn_jpeg_dhuff(const unsigned char* blob, long blob_len, const long long* de
                    const long long* seg, const long long* sub_base, const int* wgtab, int N, long nseg, long nsub, int nwg, int rounds, short* coef,
                    long coef_elems, void* ws, long ws_bytes, unsigned long long* res, void* stream);
 
+/* ---- PNG at both ends of the device pipeline (csrc/png.hip): zlib's inflate and deflate stay on the host (db_text_minimal_amd/png.py); the
+ * scanline filters, Adam7, the sample conversions and the packing run on the device.  Pixels are cv2.imread's IMREAD_COLOR ones, as RGB.
+ * desc int64 [N][32] per image = {width, height, bit depth, colour type, interlace, output byte offset, palette entries, status (not 0: the
+ * image takes no bytes anywhere), src[8], raw[8], 0 ...}: src[s] / raw[s] are the byte offsets of sub-image s in the blob of filtered scanlines
+ * and in the workspace of reconstructed ones; s = 0 is the whole image of a file that is not interlaced, s = 1 .. 7 the Adam7 passes of one
+ * that is.  A sub-image of ph rows of rb bytes takes ph (rb + 1) bytes in the blob (a type byte, at most 4, in front of every row) and ph rows of
+ * rb rounded up to 16 in the workspace; the sub-images lie end to end in both, in image and pass order, and the blob holds nothing else.  Output
+ * offsets are packed in image order.  subs int32 [n_subs][2] =
+ * {image, s}: the sub-images that hold bytes, one workgroup each.  Every entry point takes the descriptors twice, in host memory (hdesc,
+ * hsubs), which it checks against the buffer lengths before anything is launched, and in device memory, which the kernels read.
+ * dbn_png_check (host): the checks alone.  dbn_png_unfilter (one launch): blob is 4-byte aligned and blob_cap >= blob_len + 32 bytes are
+ * allocated.  dbn_png_pixels (one launch): palettes uint8 [N][256][3]; packed uint8 [H][W][3] per image.
+ * dbn_png_filter_rows (encode, one launch): desc int64 [N][8] = {input byte offset, H, W, channels (1 or 3), output byte offset, first row over
+ * the batch, 0, 0}; out receives H rows of 1 + W channels bytes per image: the type byte and the filtered row.  filter 0 .. 4: that type for
+ * every row; -1: per row the type whose sum of min(f, 256 - f) is lowest, the lowest type of equal ones. */
+int dbn_png_check(const long long* hdesc, int N, const int* hsubs, int n_subs, long blob_len, long raw_bytes, long out_bytes);
+int dbn_png_unfilter(const unsigned char* blob, long blob_len, long blob_cap, const long long* hdesc, const long long* desc, int N,
+                     const int* hsubs, const int* subs, int n_subs, unsigned char* raw, long raw_bytes, long out_bytes, void* stream);
+int dbn_png_pixels(const unsigned char* raw, long raw_bytes, const long long* hdesc, const long long* desc, const unsigned char* palettes, int N,
+                   long blob_len, unsigned char* out, long out_bytes, void* stream);
+int dbn_png_filter_rows(const unsigned char* pixels, long in_bytes, const long long* hdesc, const long long* desc, int N, int filter,
+                        unsigned char* out, long out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
