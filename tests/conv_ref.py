@@ -285,6 +285,43 @@ FWD_CASES = [
 ]
 DGRAD_CASES = [c for c in FWD_CASES if c[1] % 64 == 0]  # the gradient's channel count Ci is the kernel's Cd: a multiple of 64
 WGRAD_CASES = [FWD_CASES[i] for i in (0, 2, 3, 4, 5, 6)]  # those of tests/test_ops_gpu.py WGRAD_CASES
+# The weight gradient with several pixel splits (tests/test_wgrad_fp64_gpu.py); tests/test_wgrad_cases_cpu.py asks the library's own plan
+# functions whether each case still reaches what its comment names.  P = N Ho Wo pixels, `splits` slabs of pchunk pixels each, G thread
+# groups in the slab reduction.  None of these has the pixel-patch form (W % 16 != 0, or not 3 x 3 / stride 1).
+WGRAD_SPLIT_CASES = [
+    (3, 64, 64, 3, 1, 1, 40, 36),  # P 4320, 9 splits of 480, 64 x 192, G 2: the baseline; image boundaries inside splits
+    (2, 64, 64, 3, 1, 1, 37, 59),  # P 4366 (% 16 = 14), 9 splits of 496 (% 32 = 16): a split ends inside a 32-pixel stage and inside a k-step
+    (2, 32, 64, 3, 1, 1, 37, 41),  # P 3034, 6 splits of 512, 64 x 128, G 1; Cb = 32: J = 288 padded to Jp = 384
+    (2, 96, 64, 3, 1, 1, 37, 41),  # Cb = 96, no multiple of 64: wgrad_reduce_kernel
+    (1, 64, 128, 3, 2, 1, 97, 83),  # P 2058, 5 splits of 416, 128 x 128: stride 2, odd map
+    (2, 64, 128, 1, 2, 0, 90, 94),  # P 4230, 9 splits of 480, 64 x 64, G 2: 1 x 1 / stride 2 (the downsample convs)
+    (4, 128, 64, 1, 1, 0, 45, 47),  # P 8460, 17 splits of 512, 64 x 128, G 4: 1 x 1
+    (2, 64, 64, 2, 2, 0, 100, 96),  # P 4800, 10 splits of 480, G 2: the geometry of the ConvTranspose2d weight gradient
+    (2, 64, 64, 4, 2, 1, 90, 94),  # P 4230, 9 splits of 480, G 2: FPN level 1 (k = f + 2, stride f)
+    (2, 3, 64, 7, 2, 3, 97, 99),  # P 4900, 10 splits of 496: the stem, Cb = 4 (fp32 tensors) or 16 (bf16 storage), I = 3
+]
+# 3 x 3 / stride 1 / pad 1 with H % 4 == 0 and W % 16 == 0: wgrad_patch_kernel in the 16-bit matrix modes, splits over 4 x 16 patches
+WGRAD_PATCH_CASES = [
+    (2, 64, 64, 3, 1, 1, 48, 48),  # 72 patches, 9 splits of 8, G 2: the baseline
+    (3, 64, 64, 3, 1, 1, 44, 48),  # 99 patches, 13 splits of 8, G 3: the last split partial; three images
+    (2, 64, 192, 3, 1, 1, 36, 32),  # 36 patches, 5 splits: three output-channel blocks
+    (2, 128, 64, 3, 1, 1, 36, 32),  # 36 patches, 5 splits: two input-channel blocks
+    (1, 256, 256, 3, 1, 1, 60, 240),  # 225 patches, 28 splits of 9, G 7: 25 splits hold patches, 3 write zero slabs
+]
+
+
+def wgrad_x_seams(case):
+    """Pixels (n, h, w) of x at which a weight-gradient kernel's gather goes wrong first: the four corners, the whole last row and
+    column, the input pixel of the output pixel on each side of every multiple of 16 flattened output pixels (split boundaries, k-steps,
+    32-pixel LDS stages) and, on the pixel-patch cases, the four pixels around every 4 x 16 patch corner (the halo of the 18-wide rows)."""
+    N, Ci, Co, k, s, p, H, W = case
+    Ho, Wo = out_size(H, k, s, p), out_size(W, k, s, p)
+    extra = [(0, W - 1), (H - 1, 0)] + [(H - 1, w) for w in range(W)] + [(h, W - 1) for h in range(H)]
+    if case in WGRAD_PATCH_CASES:
+        extra += [(h, w) for i in range(4, H, 4) for j in range(16, W, 16) for h in (i - 1, i) for w in (j - 1, j)]
+    return seam_pixels(N, H, W, Ho, Wo, s, tile_rows=16, extra=extra)
+
+
 SPLITK_CASES = [(1, 512, 512, 3, 1, 1, 10, 12), (2, 256, 64, 10, 8, 1, 40, 40)]
 KSPLITS = (2, 5, 7)
 CONVT2 = (2, 64, 64, 8, 6)  # N, Ci, Co, H, W: ConvTranspose2d(k = 2, stride 2)

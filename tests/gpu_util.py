@@ -105,15 +105,27 @@ def wgrad(sm, big, O, I, k, stride, pad, scale=1.0, ns=0):
     return g
 
 
-def wgrad_t(sm, big, O, I, k, stride, pad, ns=0, scale=1.0):
-    """dbn_wgrad_t on fp32 / bf16 tensors (sm: the output-side tensor [N, Ho, Wo, O], big: the input side [N, H, W, Cb]) with a NaN-filled
-    slab and gradient."""
+def wgrad_t_call(sm, big, O, I, k, stride, pad, ns=0, scale=1.0):
+    """A NaN-filled slab, a NaN-filled gradient and the arguments of a dbn_wgrad_t / dbn_wgrad_phase_t / dbn_wgrad_reduce_describe call
+    on them (all but the last one: the stream, or the job record)."""
+    assert sm.dtype == big.dtype and sm.is_contiguous() and big.is_contiguous()
     N, Ho, Wo, _ = sm.shape
     _, H, W, Cb = big.shape
     slab = torch.full((L().dbn_wgrad_slab_floats_hw(N, Ho, Wo, O, H, W, Cb, k, k, big.element_size()), ), float('nan'), device=DEV)
     g = torch.full((O, I, k, k), float('nan'), device=DEV)
-    _lib.check(L().dbn_wgrad_t(AT_OF[big.dtype], ns, sm.data_ptr(), big.data_ptr(), slab.data_ptr(), g.data_ptr(), N, Ho, Wo, O, H, W, Cb, I, k, k,
-                               stride, pad, scale, stream()), 'wgrad_t')
+    return slab, g, (AT_OF[big.dtype], ns, sm.data_ptr(), big.data_ptr(), slab.data_ptr(), g.data_ptr(), N, Ho, Wo, O, H, W, Cb, I, k, k, stride,
+                     pad, scale)
+
+
+def wgrad_t(sm, big, O, I, k, stride, pad, ns=0, scale=1.0, phases=False):
+    """dbn_wgrad_t on fp32 / bf16 tensors (sm: the output-side tensor [N, Ho, Wo, O], big: the input side [N, H, W, Cb]) with a NaN-filled
+    slab and gradient; phases: as dbn_wgrad_phase_t(1) followed by (2)."""
+    slab, g, args = wgrad_t_call(sm, big, O, I, k, stride, pad, ns, scale)
+    if phases:
+        _lib.check(L().dbn_wgrad_phase_t(1, *args, stream()), 'wgrad_phase_t(1)')
+        _lib.check(L().dbn_wgrad_phase_t(2, *args, stream()), 'wgrad_phase_t(2)')
+    else:
+        _lib.check(L().dbn_wgrad_t(*args, stream()), 'wgrad_t')
     return g
 
 

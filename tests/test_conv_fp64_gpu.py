@@ -1,5 +1,7 @@
 """-m gpu: the convolution kernels (direct implicit GEMM in its three matrix modes and on 16-bit storage, split-K, ConvTranspose2d, the
-weight gradient, Winograd forward / data gradient / weight gradient) against the float64 reference of tests/conv_ref.py.
+weight gradient, Winograd forward / data gradient / weight gradient) against the float64 reference of tests/conv_ref.py.  The weight-gradient
+cases here fit one or two pixel splits; tests/test_wgrad_fp64_gpu.py pins the same entry point with many splits, in the pixel-patch kernel, on
+stored-bf16 operands (the "-" of the wgrad rows below) and through the grouped slab reduction.
 
 Three kinds of case per kernel:
   * random data: the kernel's distance to float64 is measured against the distance of plain fp32 (F.conv2d / autograd in fp32 on the CPU,

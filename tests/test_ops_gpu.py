@@ -1416,7 +1416,7 @@ def test_weight_gradient_on_bf16_storage(case, variant):
     (gref, ) = torch.autograd.grad(y, w, dy.to(torch.bfloat16).double())
     xs, dys = nhwc(x).to(torch.bfloat16), nhwc(dy).to(torch.bfloat16)
     Ho, Wo = y.shape[2], y.shape[3]
-    slab = torch.empty(L().dbn_wgrad_slab_floats(N, Ho, Wo, Co, Ci, k, k), device=DEV)
+    slab = torch.full((L().dbn_wgrad_slab_floats(N, Ho, Wo, Co, Ci, k, k), ), float('nan'), device=DEV)  # an element nobody wrote shows
     g = torch.full((Co, Ci, k, k), float('nan'), device=DEV)
     try:
         _lib.check(L().dbn_set_wgrad_variant(variant), 'variant')
@@ -1763,9 +1763,10 @@ def test_pixel_patch_weight_gradient(case, mode_name):
     (gref, ) = torch.autograd.grad(F.conv2d(rq(x), w, None, 1, 1), w, rq(dy))
     dt = torch.bfloat16 if at == 1 else torch.float32
     xs, dys = nhwc(x).to(dt), nhwc(dy).to(dt)
-    slab = torch.empty(L().dbn_wgrad_slab_floats_hw(N, H, W, Co, H, W, Ci, 3, 3, 2 if at == 1 else 4), device=DEV)
+    slab_floats = L().dbn_wgrad_slab_floats_hw(N, H, W, Co, H, W, Ci, 3, 3, 2 if at == 1 else 4)
 
     def run(variant):
+        slab = torch.full((slab_floats, ), float('nan'), device=DEV)  # per launch: an element nobody wrote shows
         g = torch.full((Co, Ci, 3, 3), float('nan'), device=DEV)
         try:
             _lib.check(L().dbn_set_wgrad_variant(variant), 'variant')
