@@ -12,6 +12,10 @@ collective; optionally the same sum as four contiguous buckets issued in the ord
 backward pass completes them — `overlap_allreduce`); the 1/world average is folded
 into the Adam kernel.  BatchNorm statistics
 and the loss normalisers stay per GPU (standard data-parallel semantics).
+
+Gradient accumulation (`FusedAdam(accumulation_steps=k)`, optim.py): every call of `DBTrainer.step` runs forward, loss and
+backward on its micro-batch and folds the flat gradient into the optimizer's accumulator; the k-th call of a cycle then
+exchanges the ACCUMULATOR (one all-reduce per cycle: k times fewer collectives) and updates with grad_scale = 1 / (world k).
 """
 import os
 
@@ -121,6 +125,10 @@ class DBTrainer:
         # (DBN_OVERLAP_ALLREDUCE=1, bench.py --bucketed-allreduce) issues the same sum as four contiguous buckets under the
         # backward pass instead (bit-identical results, tests/test_dp_gloo.py, tests/test_rccl_gpu.py).
         self.overlap_allreduce = os.environ.get('DBN_OVERLAP_ALLREDUCE', '0') == '1'
+        # Gradient accumulation: k = optimizer.accumulation_steps calls of step() make one update (module docstring).  The bucketed
+        # exchange reduces the flat gradient of ONE backward pass while that pass runs — one k-th of the sum an update needs.
+        self._check_accumulation()
+        self.updated = False  # did the last step() call end with an optimizer update?  (fit(): per-update schedulers)
         # Replicas start from rank 0's state.  The broadcast is the first collective, and the first collective creates the
         # RCCL communicator — which should happen AFTER the activation arena exists (init_distributed: creating it first
         # cost 2.4 ms/step at bs16 640^2).  So the sync is deferred to the first step(), which knows the batch shape: it
@@ -150,6 +158,18 @@ class DBTrainer:
         self.gc_freeze = (os.environ.get('DBN_GC_FREEZE', '0') == '1') if gc_freeze is None else bool(gc_freeze)
         self._froze = False
         self._steps = 0
+
+    @property
+    def accumulation_steps(self):
+        return int(getattr(self.optimizer, 'accumulation_steps', 1))
+
+    def _check_accumulation(self):
+        k = self.accumulation_steps
+        if k > 1 and self.overlap_allreduce:
+            raise RuntimeError('overlap_allreduce (DBN_OVERLAP_ALLREDUCE=1) reduces the gradient of one backward pass while it runs; with '
+                               'accumulation_steps=%d the exchange is ONE all-reduce of the accumulated sum per update — use one or the '
+                               'other' % k)
+        return k
 
     def freeze_heap(self):
         """gc.collect() + gc.freeze(): every object alive in this PROCESS now leaves the cyclic collector's generations, so the
@@ -190,6 +210,8 @@ class DBTrainer:
             opt.step_count = int(cnt.item())
             dist.broadcast(opt.exp_avg, src=src, group=self.pg)
             dist.broadcast(opt.exp_avg_sq, src=src, group=self.pg)
+            if opt.max_exp_avg_sq is not None:
+                dist.broadcast(opt.max_exp_avg_sq, src=src, group=self.pg)
         eng.mark_params_dirty()
         self._need_sync = False
 
@@ -272,7 +294,9 @@ class DBTrainer:
         as `img`, with gts=None).  Returns (preds, losses[5]) as device tensors; no host sync.
         `resident=True` (hipGraph step only) is the caller's promise that `img` / `gts` are the very tensors of the previous
         call, unmodified (bench.py's synthetic batch): the copy into the graph's static inputs is skipped.  Nothing is
-        inferred from object identity — a new batch is always copied."""
+        inferred from object identity — a new batch is always copied.
+        With optimizer.accumulation_steps = k > 1 every call runs forward, loss and backward; calls 1 .. k-1 of a cycle end with the
+        fold into the accumulator, call k folds, exchanges the accumulator and updates (`self.updated` tells which it was)."""
         if isinstance(img, dict):
             batch = img
             img, gts = batch['img'], stack_gts(batch)
@@ -286,15 +310,19 @@ class DBTrainer:
         if self._need_sync:
             self._warm_arena_then_sync(img, gts)
         distributed = self.distributed
+        self._check_accumulation()  # (overlap_allreduce may have been set after construction)
         if self.use_graph and eng.prof is None and not (distributed and self.overlap_allreduce):
+            if self.accumulation_steps > 1:
+                # A replay is the same work every time, so the graph always holds the batched repack of the weight panels (with one update
+                # per call every forward pass finds them stale).  Under accumulation only a cycle's first call does, so every call —
+                # the eager warm-up ones too: they build the repack's job table — declares them stale: repacking unchanged weights
+                # rewrites the same bits (0.13 ms), and a graph captured on a cycle's later call is not left without the repack.
+                eng.mark_params_dirty()
             self.optimizer.zero_grad()  # (before the backward pass, as on the eager path: the replay below counts as ONE pass)
             got = self._graph_step(img, gts, resident)
             if got is not None:
                 preds, losses = got
-                ev = self._exchange_event()
-                scale = allreduce_flat_grads(eng.flat_grad, self.world, self.pg) if distributed else 1.0
-                self._exchange_event(ev)
-                self.optimizer.step(grad_scale=scale)
+                self._exchange_and_update(distributed)  # (fold, norm and update stay outside the graph, like Adam)
                 return preds, losses
         preds = eng.forward(img, train=True)
         assert preds.size(1) == 3  # train.py:161
@@ -311,13 +339,29 @@ class DBTrainer:
             ev = self._exchange_event()  # backward fully enqueued: what the exchange still takes from here on is exposed
             scale = ex.finish()
             self._exchange_event(ev)
+            self.optimizer.step(grad_scale=scale)
+            self.updated = True
         else:
             eng.backward(dpreds)
-            ev = self._exchange_event()
-            scale = allreduce_flat_grads(eng.flat_grad, self.world, self.pg) if distributed else 1.0
-            self._exchange_event(ev)
-        self.optimizer.step(grad_scale=scale)
+            self._exchange_and_update(distributed)
         return preds, losses
+
+    def _exchange_and_update(self, distributed):
+        """After the backward pass: the one all-reduce and the optimizer.  Under accumulation the flat gradient is folded first, the
+        cycle's last call exchanges the accumulator, and the update takes the mean over ranks AND passes."""
+        opt, k = self.optimizer, self.accumulation_steps
+        grad = self.model.engine.flat_grad
+        self.updated = False
+        if k > 1:
+            opt.accumulate()
+            if opt.folded < k:
+                return
+            grad = opt.grad_acc
+        ev = self._exchange_event()
+        scale = allreduce_flat_grads(grad, self.world, self.pg) if distributed else 1.0
+        self._exchange_event(ev)
+        opt.step(grad_scale=scale if k == 1 else scale / k)
+        self.updated = True
 
     def _graph_step(self, img, gts, resident=False):
         """forward + loss + backward through a captured hipGraph; None while still warming up (the caller takes the eager path).
@@ -517,7 +561,8 @@ def fit(model, criterion, optimizer, train_loader, test_loader=None, epochs=1, s
         best_cp_path=None, last_cp_path=None, device=None, log=None, process_group=None, trainer=None, pixel_metric=True,
         detection=None, best_hmean_cp_path=None):
     """The reference's training driver (train.py:146-318): per epoch a pass over `train_loader` through DBTrainer.step
-    (lr scheduler stepped per iteration when lrs_mode == 'poly', train.py:172-173), the running pixel metric
+    (lr scheduler stepped per iteration when lrs_mode == 'poly', train.py:172-173 — per UPDATE under gradient accumulation:
+    on the last call of each cycle of optimizer.accumulation_steps; `global_steps` counts every call), the running pixel metric
     (train.py:175-181, on device), then evaluate() on `test_loader`, the reference's best-checkpoint rule
     (`test_loss <= best_test_loss and train_loss <= best_train_loss`, train.py:301-305; `train_loss` is the epoch SUM as
     there), ReduceLROnPlateau-style schedulers stepped with the test loss when lrs_mode == 'reduce' (train.py:307-308), and
@@ -567,7 +612,7 @@ def fit(model, criterion, optimizer, train_loader, test_loader=None, epochs=1, s
                 batch = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
             steps += 1
             preds, losses = trainer.step(batch, None)
-            if lrs_mode == 'poly' and scheduler is not None:
+            if lrs_mode == 'poly' and scheduler is not None and getattr(trainer, 'updated', True):
                 scheduler.step()
             if running is not None:
                 running.update_device(preds[:, 0, :, :], batch['prob_map'], batch['supervision_mask'], thresh)

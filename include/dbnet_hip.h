@@ -368,6 +368,23 @@ int dbn_pixel_confusion(const float* preds, long batch_stride, const float* gt, 
 int dbn_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps, int step,
                   float grad_scale, void* stream);
 
+/* ---- optimizer extensions (csrc/optim.hip): gradient accumulation, the global gradient norm, and Adam with AMSGrad, L2 weight decay
+ *      and norm clipping.  Nothing here crosses to the host: the norm stays in device memory and the Adam launch reads it there.
+ * dbn_grad_accumulate: acc = g when `first`, else acc += g (one fp32 add per element, the k micro-batches of one update in pass order).
+ * dbn_grad_sqnorm: out[0] = sum of g[i]^2 in float64.  Workgroup b sums the fixed chunk [b C, (b + 1) C) of g into partials[b]
+ *      (C is a compile-time constant, so the partition depends on n alone); a second launch of one workgroup adds the partials in index
+ *      order.  No atomics: the same bits on every run.  `partials` holds dbn_grad_sqnorm_ws_doubles(n) doubles and needs no clearing.
+ * dbn_adam_step_ex: with s = grad_scale,
+ *      coef = sqnorm ? min(1, max_norm / (|s| sqrt(*sqnorm) + 1e-6)) : 1        (torch.nn.utils.clip_grad_norm_; a NaN norm gives NaN)
+ *      gg = (coef s) g + weight_decay p                                          (torch's L2 form: the decay enters after the clip)
+ *      then dbn_adam_step's update on gg, with vmax = max(vmax, v) in place of v under the square root when vmax != NULL (AMSGrad).
+ *      With vmax == NULL, sqnorm == NULL and weight_decay == 0 the results are bit-identical to dbn_adam_step's. */
+int dbn_grad_accumulate(float* acc, const float* g, long n, int first, void* stream);
+long dbn_grad_sqnorm_ws_doubles(long n);
+int dbn_grad_sqnorm(const float* g, long n, double* partials, double* out, void* stream);
+int dbn_adam_step_ex(float* p, const float* g, float* m, float* v, float* vmax, long n, float lr, float beta1, float beta2, float eps,
+                     float weight_decay, int step, float grad_scale, const double* sqnorm, float max_norm, void* stream);
+
 /* 1 when the library was built with -DDBN_EXPERIMENTS (make -C csrc EXP=1): adds the variants that were measured and rejected —
  * pre-split bf16 planes (at = 3, dbn_split3), the LDS-DMA fp32 weight gradient (dbn_set_wgrad_variant(1)), DBN_* environment
  * overrides of the tile / split heuristics.  The product library (default) has none of them: no getenv anywhere. */
