@@ -9,7 +9,8 @@ data_loaders.py:161-167, so a DataLoader ships decoded uint8 images of any size 
   plan_letterbox(shapes, polys, size)        host: the evaluation plan (letterbox only)
   augment_images(packed, shapes, plans)      device: fp32 [N, 3, S, S], normalised; plans=None is the letterbox
   preprocess_image(u8, size, pad)            device: utils.test_preprocess of one image
-  DeviceBatches(loader, device, training)    raw batches -> the dicts fit / evaluate consume (img + GT maps)
+  DeviceBatches(loader, device, training)    raw batches -> the dicts fit / evaluate consume (img + GT maps); with
+                                             color_jitter the photometric stage (photometric.py) runs in front
 
 Device stages (csrc/resample.hip), one launch each per batch on the current stream, no host sync: warp (flip + rotate,
 cv2.warpAffine INTER_LINEAR) -> cubic resize of the crop window only (cv2.resize INTER_CUBIC) -> linear letterbox resize
@@ -33,6 +34,7 @@ import torch
 from ._lib import check, lib
 from .gt_maps import GT_KEYS, MEAN, make_gt_maps, plan_polygons
 from .jpeg import JpegCoefficients, JpegStreams, decode_coefficients, entropy_decode_device, stream_orientations
+from .photometric import color_jitter_images, color_jitter_ranges, plan_color_jitter
 from .png import PngScanlines, unfilter_png
 
 ROTATE = (-10.0, 10.0)  # data_loaders.py:62-66
@@ -398,12 +400,25 @@ class DeviceBatches:
     (per image, the scaled polygons) and `ignore_tags` (per image, the GT ignore flags) as the reference's test loader
     returns them.  orient=True: JPEG batches are decoded with their Exif orientation applied (decode_coefficients), as the
     reference's cv2.imread does; the polygons are then those of the displayed image.  gt_kwargs go to make_gt_maps
-    (shrink_ratio, thresh_min, thresh_max, min_text_size, ignore_tags)."""
+    (shrink_ratio, thresh_min, thresh_max, min_text_size, ignore_tags).  color_jitter: a dict of plan_color_jitter's
+    keyword arguments (brightness, contrast, saturation, hue), e.g. {'brightness': 32 / 255, 'saturation': 0.5}; with
+    training=True the decoded uint8 batch then goes through color_jitter_images in front of the geometric steps, where
+    MMOCR's DBNet pipeline has its ColorJitter.  Its plans are drawn from a second RandomState (seeded with
+    [seed, JITTER_STREAM]), so the geometric plans of a seed are the same with and without it; None (the default), or
+    arguments that leave no operation present, make no draw and no launch."""
 
-    def __init__(self, loader, device, training, size=640, seed=None, mean=MEAN, orient=False, **gt_kwargs):
+    JITTER_STREAM = 0x636A  # second word of the colour stream's seed
+
+    def __init__(self, loader, device, training, size=640, seed=None, mean=MEAN, orient=False, color_jitter=None, **gt_kwargs):
         self.loader, self.device, self.training, self.size, self.mean = loader, torch.device(device), bool(training), int(size), mean
         self.orient = bool(orient)
         self.rng = np.random.RandomState(seed)
+        self.color_jitter = self.jitter_rng = None
+        # (a bad range or key raises here, not in the first batch)
+        if color_jitter is not None and color_jitter_ranges(**color_jitter):
+            self.color_jitter = dict(color_jitter)
+            words = None if seed is None else np.append(np.asarray(seed, np.uint32).reshape(-1), np.uint32(self.JITTER_STREAM))
+            self.jitter_rng = np.random.RandomState(words)
         self.gt_kwargs = gt_kwargs
 
     def __len__(self):
@@ -423,6 +438,11 @@ class DeviceBatches:
         if isinstance(packed, PngScanlines):  # png_collate: the device half of the decode
             packed, shapes = unfilter_png(packed, self.device)
         if self.training:
+            if self.color_jitter is not None:
+                if not (isinstance(packed, torch.Tensor) and packed.is_cuda):  # image_collate's pinned host batch
+                    packed = _packed(packed, shapes, self.device)
+                colour_plans = plan_color_jitter(len(shapes), self.jitter_rng, **self.color_jitter)
+                packed = color_jitter_images(packed, shapes, colour_plans)
             plans = plan_augment(shapes, polys, self.rng, self.size)
         else:
             plans = plan_letterbox(shapes, polys, self.size)

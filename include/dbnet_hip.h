@@ -1059,6 +1059,24 @@ int dbn_png_pixels(const unsigned char* raw, long raw_bytes, const long long* hd
 int dbn_png_filter_rows(const unsigned char* pixels, long in_bytes, const long long* hdesc, const long long* desc, int N, int filter,
                         unsigned char* out, long out_bytes, void* stream);
 
+/* ---- Photometric augmentation (csrc/photometric.hip, csrc/photometric.h; db_text_minimal_amd/photometric.py): torchvision's ColorJitter as
+ * it acts on PIL images (Pillow's Image.blend, convert('L'), convert('HSV') and back), bit for bit, on packed uint8 [H][W][3] RGB images.
+ * desc int64 [N][8] per image = {byte offset of its first pixel (any alignment; ascending, images do not overlap), H, W, first chunk over the
+ * batch (an image takes ceil(H W / 1024) chunks; images in order), ops, f01, f23, 0}.  ops = steps (0 .. 4) | code of step k << 4 (k + 1), codes
+ * 1 brightness, 2 contrast, 3 colour (torchvision's saturation), 4 hue, each at most once, in the order they are applied; f01 / f23 hold 32 bits
+ * per step (step 0 in the low half of f01): the bits of the float32 factor (finite), or for hue the shift 0 .. 255 added to H mod 256.
+ * 1 <= N <= 65535, 1 <= H, W <= 16384.  The records are taken twice: in host memory (hdesc), checked against `bytes` before anything is
+ * launched, and in device memory (desc), which the kernels read.
+ * dbn_color_jitter_u8 (a memset and a launch for the grey sums when a plan holds contrast, then one launch): sums uint64 [N] of workspace
+ * (may be NULL when no plan holds contrast).  out == in works in place; bytes of `out` that belong to no image are not written.
+ * dbn_color_jitter_host: TEST SUPPORT, not a product path (no Python function calls it, and the package refuses host tensors): the same
+ * arithmetic (csrc/photometric.h compiled for the host) walked over host buffers without a launch, so that the tests that run without a
+ * device hold what this library compiles, not only its numpy restatement, against Pillow.  It is declared here because every dbn_* symbol
+ * the library defines is (tests/test_host_cpu.py), and the ctypes side is derived from this header alone. */
+int dbn_color_jitter_u8(const unsigned char* in, unsigned char* out, long bytes, const long long* hdesc, const long long* desc, int N,
+                        unsigned long long* sums, void* stream);
+int dbn_color_jitter_host(const unsigned char* in, unsigned char* out, long bytes, const long long* hdesc, int N);
+
 #ifdef __cplusplus
 }
 #endif
