@@ -34,13 +34,14 @@ import torch
 from ._lib import check, lib
 from .gt_maps import GT_KEYS, MEAN, make_gt_maps, plan_polygons
 from .jpeg import JpegCoefficients, JpegStreams, decode_coefficients, entropy_decode_device, stream_orientations
+from .packed import MAX_SIDE, check_shape, cuda_device, image_offsets, on_device, packed_on, pin_default, polys_tags, upload
+from .packed import offsets as _offsets
 from .photometric import color_jitter_images, color_jitter_ranges, plan_color_jitter
 from .png import PngScanlines, unfilter_png
 
 ROTATE = (-10.0, 10.0)  # data_loaders.py:62-66
 SCALE = (0.5, 3.0)
 _DESC, _COEF = 12, 6
-_MAX_SIDE = 65535
 
 
 # ---- host plan -----------------------------------------------------------------------------------------------------
@@ -152,13 +153,6 @@ def _polys_of(polys, i):
     return [np.asarray(p, np.float64).reshape(-1, 2) for p in (polys[i] if polys is not None else [])]
 
 
-def _check_shape(shape):
-    H, W = int(shape[0]), int(shape[1])
-    if not (1 <= H <= _MAX_SIDE and 1 <= W <= _MAX_SIDE):
-        raise ValueError('image size %d x %d outside 1 .. %d' % (H, W, _MAX_SIDE))
-    return H, W
-
-
 def _letterbox_plan(plan, h, w, polys, size):
     s, nh, nw, out = letterbox(h, w, polys, size)
     if nh < 1 or nw < 1:
@@ -174,12 +168,12 @@ def plan_augment(shapes, polys, rng, size=640, rotate=ROTATE, scale=SCALE):
     of the source polygons that survive the crop, for their tags)."""
     plans = []
     for i, shape in enumerate(shapes):
-        H, W = _check_shape(shape)
+        H, W = check_shape(shape)
         flip = bool(rng.random_sample() < 0.5)
         angle = float(rng.uniform(*rotate))
         sc = float(rng.uniform(*scale))
         h2, w2 = max(1, int(round(H * sc))), max(1, int(round(W * sc)))
-        if h2 > _MAX_SIDE or w2 > _MAX_SIDE:
+        if h2 > MAX_SIDE or w2 > MAX_SIDE:
             raise ValueError('image %d scales to %d x %d' % (i, h2, w2))
         M = rotation_matrix(angle, H, W)
         moved = []
@@ -203,7 +197,7 @@ def plan_letterbox(shapes, polys=None, size=640):
     polys (fp64, scaled) and keep (every polygon)."""
     plans = []
     for i, shape in enumerate(shapes):
-        H, W = _check_shape(shape)
+        H, W = check_shape(shape)
         src = _polys_of(polys, i)
         plan = dict(flip=False, angle=None, scale=None, M=None, src_hw=(H, W), scaled_hw=(H, W), window=(0, H, 0, W),
                     keep=list(range(len(src))))
@@ -212,39 +206,9 @@ def plan_letterbox(shapes, polys=None, size=640):
 
 
 # ---- device stages -------------------------------------------------------------------------------------------------
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _to_device(a, dev):
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return t.pin_memory().to(dev, non_blocking=True)
-
-
-def _offsets(sizes):
-    off = np.zeros(len(sizes) + 1, np.int64)
-    off[1:] = np.cumsum(np.asarray(sizes, np.int64))
-    return off
-
-
 def _resize_coef(src, dst):
     """cv2.resize: inv_scale = (double)dst / src, scale = 1. / inv_scale"""
     return 1. / (float(dst) / float(src))
-
-
-def _device_of(packed_u8, device):
-    if device is not None:
-        return torch.device(device)
-    return packed_u8.device if packed_u8.is_cuda else torch.device('cuda', torch.cuda.current_device())
-
-
-def _packed(packed_u8, shapes, dev):
-    if packed_u8.dtype != torch.uint8 or packed_u8.dim() != 1:
-        raise ValueError('packed_u8 must be a flat uint8 tensor (image_collate)')
-    need = int(sum(int(h) * int(w) * 3 for h, w in shapes))
-    if packed_u8.numel() != need:
-        raise ValueError('packed_u8 holds %d bytes, the shapes need %d' % (packed_u8.numel(), need))
-    return packed_u8.to(dev, non_blocking=True).contiguous()
 
 
 def letterbox_args(src_off, src_hw, plans, CH, CW):
@@ -266,10 +230,11 @@ def _letterbox_launch(src, src_off, src_hw, plans, CH, CW, mean, dev):
     N = len(plans)
     desc, coef = letterbox_args(src_off, src_hw, plans, CH, CW)
     out = torch.empty((N, 3, CH, CW), device=dev, dtype=torch.float32)
-    d, c = _to_device(desc, dev), _to_device(coef, dev)
     m = [float(np.float32(v)) for v in mean]
-    check(lib().dbn_resize_linear_norm_u8(src.data_ptr(), src.numel(), d.data_ptr(), c.data_ptr(), N, CH, CW, m[0], m[1], m[2],
-                                          out.data_ptr(), _stream(dev)), 'resize_linear_norm_u8')
+    with on_device(dev) as st:
+        d, c = upload(desc, dev), upload(coef, dev)
+        check(lib().dbn_resize_linear_norm_u8(src.data_ptr(), src.numel(), d.data_ptr(), c.data_ptr(), N, CH, CW, m[0], m[1], m[2],
+                                              out.data_ptr(), st), 'resize_linear_norm_u8')
     return out
 
 
@@ -290,9 +255,10 @@ def warp_stage(src, src_off, shapes, plans, dev):
     """launch 1: flip + rotate (dbn_warp_affine_u8) -> packed uint8 warped images, laid out as the source"""
     desc, coef, max_h, max_w = warp_args(src_off, shapes, plans)
     warped = torch.empty(int(src_off[-1]), device=dev, dtype=torch.uint8)
-    d, c = _to_device(desc, dev), _to_device(coef, dev)
-    check(lib().dbn_warp_affine_u8(src.data_ptr(), src.numel(), d.data_ptr(), c.data_ptr(), len(shapes), max_h, max_w,
-                                   warped.data_ptr(), warped.numel(), _stream(dev)), 'warp_affine_u8')
+    with on_device(dev) as st:
+        d, c = upload(desc, dev), upload(coef, dev)
+        check(lib().dbn_warp_affine_u8(src.data_ptr(), src.numel(), d.data_ptr(), c.data_ptr(), len(shapes), max_h, max_w,
+                                       warped.data_ptr(), warped.numel(), st), 'warp_affine_u8')
     return warped
 
 
@@ -303,10 +269,10 @@ def cubic_args(src_off, shapes, plans):
     for p in plans:
         y0, y1, x0, x1 = p['window']
         h2, w2 = p['scaled_hw']
-        if not (0 <= y0 < y1 <= h2 and 0 <= x0 < x1 <= w2 and h2 <= _MAX_SIDE and w2 <= _MAX_SIDE):
+        if not (0 <= y0 < y1 <= h2 and 0 <= x0 < x1 <= w2 and h2 <= MAX_SIDE and w2 <= MAX_SIDE):
             raise ValueError('crop window %s outside the %d x %d scaled image' % (p['window'], h2, w2))
         win_hw.append((y1 - y0, x1 - x0))
-    dst_off = _offsets([h * w * 3 for h, w in win_hw])
+    dst_off = image_offsets(win_hw)
     desc = np.zeros((N, _DESC), np.int64)
     coef = np.zeros((N, _COEF), np.float64)
     for n, ((H, W), p, (ch, cw)) in enumerate(zip(shapes, plans, win_hw)):
@@ -322,16 +288,17 @@ def cubic_stage(warped, src_off, shapes, plans, dev):
     byte offsets, their (h, w))"""
     desc, coef, dst_off, win_hw, max_h, max_w = cubic_args(src_off, shapes, plans)
     cropped = torch.empty(int(dst_off[-1]), device=dev, dtype=torch.uint8)
-    d, c = _to_device(desc, dev), _to_device(coef, dev)
-    check(lib().dbn_resize_cubic_u8(warped.data_ptr(), warped.numel(), d.data_ptr(), c.data_ptr(), len(shapes), max_h, max_w,
-                                    cropped.data_ptr(), cropped.numel(), _stream(dev)), 'resize_cubic_u8')
+    with on_device(dev) as st:
+        d, c = upload(desc, dev), upload(coef, dev)
+        check(lib().dbn_resize_cubic_u8(warped.data_ptr(), warped.numel(), d.data_ptr(), c.data_ptr(), len(shapes), max_h, max_w,
+                                        cropped.data_ptr(), cropped.numel(), st), 'resize_cubic_u8')
     return cropped, dst_off, win_hw
 
 
 def augment_images(packed_u8, shapes, plans, size=640, mean=MEAN, device=None):
     """packed uint8 images (image_collate; host or device) -> fp32 [N, 3, size, size] on the device, normalised, after
     the plans' warp, cubic resize and crop, and the letterbox.  plans=None: the evaluation letterbox alone."""
-    shapes = [_check_shape(s) for s in shapes]
+    shapes = [check_shape(s) for s in shapes]
     N, S = len(shapes), int(size)
     if N == 0:
         raise ValueError('augment_images needs at least one image')
@@ -339,11 +306,9 @@ def augment_images(packed_u8, shapes, plans, size=640, mean=MEAN, device=None):
         plans = plan_letterbox(shapes, None, S)
     if len(plans) != N:
         raise ValueError('one plan per image')
-    dev = _device_of(packed_u8, device)
-    if dev.type != 'cuda':
-        raise ValueError('augment_images runs on a GPU device, not %s' % dev)
-    src = _packed(packed_u8, shapes, dev)
-    src_off = _offsets([h * w * 3 for h, w in shapes])
+    dev = cuda_device('augment_images', device, packed_u8)
+    src = packed_on(packed_u8, shapes, dev)
+    src_off = image_offsets(shapes)
     if all(p['M'] is None for p in plans):
         for p, hw in zip(plans, shapes):
             if p['window'] != (0, hw[0], 0, hw[1]) or tuple(p['scaled_hw']) != hw:
@@ -363,7 +328,7 @@ def preprocess_image(u8, size=640, pad=False, mean=MEAN):
     (padding 0 - mean[c])."""
     if not (u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 3 and u8.shape[2] == 3):
         raise ValueError('preprocess_image takes a uint8 [H, W, 3] device tensor')
-    H, W = _check_shape(u8.shape)
+    H, W = check_shape(u8.shape)
     plan = plan_letterbox([(H, W)], None, size)
     nh, nw = plan[0]['out_hw']
     CH, CW = (int(size), int(size)) if pad else (nh, nw)
@@ -380,17 +345,12 @@ def image_collate(items):
         if im.ndim != 3 or im.shape[2] != 3:
             raise ValueError('image_collate takes uint8 [H, W, 3] images')
     shapes = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
-    total = sum(im.size for im in imgs)
-    pin = torch.cuda.is_available() and torch.utils.data.get_worker_info() is None
-    packed = torch.empty(total, dtype=torch.uint8, pin_memory=pin)
+    off = _offsets([im.size for im in imgs])
+    packed = torch.empty(int(off[-1]), dtype=torch.uint8, pin_memory=pin_default())
     view = packed.numpy()
-    o = 0
-    for im in imgs:
+    for im, o in zip(imgs, off):
         view[o:o + im.size] = im.reshape(-1)
-        o += im.size
-    polys = [[np.asarray(p, dtype=np.float64).reshape(-1, 2) for p in b[1]] for b in items]
-    tags = [list(b[2]) if b[2] is not None else [None] * len(b[1]) for b in items]
-    return packed, shapes, polys, tags
+    return (packed, shapes) + polys_tags(items)
 
 
 class DeviceBatches:
@@ -430,9 +390,7 @@ class DeviceBatches:
             exif = stream_orientations([packed.blob[int(a):int(b)].numpy() for a, b in zip(packed.offs[:-1], packed.offs[1:])]) if self.orient else None
             packed = entropy_decode_device(packed, self.device)
             packed.orientation = exif
-            for e in packed.errors():
-                if e is not None:
-                    raise e
+            packed.raise_errors()
         if isinstance(packed, JpegCoefficients):  # jpeg_collate: the device half of the decode
             packed, shapes = decode_coefficients(packed, self.device, self.orient)
         if isinstance(packed, PngScanlines):  # png_collate: the device half of the decode
@@ -440,7 +398,7 @@ class DeviceBatches:
         if self.training:
             if self.color_jitter is not None:
                 if not (isinstance(packed, torch.Tensor) and packed.is_cuda):  # image_collate's pinned host batch
-                    packed = _packed(packed, shapes, self.device)
+                    packed = packed_on(packed, shapes, self.device)
                 colour_plans = plan_color_jitter(len(shapes), self.jitter_rng, **self.color_jitter)
                 packed = color_jitter_images(packed, shapes, colour_plans)
             plans = plan_augment(shapes, polys, self.rng, self.size)

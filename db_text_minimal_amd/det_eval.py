@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
+from .packed import on_device
 
 IOU, DETEVAL = 0, 1
 
@@ -85,8 +86,7 @@ def polygon_overlaps(gt_polys, det_polys, device=None, cull=True, prefill=None):
         if prefill is not None:
             ws.fill_(int(prefill))
             d_out.fill_(int(prefill))
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
+        with on_device(dev) as st:
             check(lib().dbn_det_eval_overlaps(base, base + o_poff, P, base + o_img, N, n_pairs, 1 if cull else 0, ws.data_ptr(),
                                               ob if n_pairs else None, ob + 8 * n_pairs, ob + 8 * n_pairs + 8 * P, st), 'det_eval_overlaps')
             host = d_out.cpu().numpy()

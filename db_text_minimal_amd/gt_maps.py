@@ -38,6 +38,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
+from .packed import stream
 
 GT_KEYS = ('prob_map', 'supervision_mask', 'thresh_map', 'text_area_map')
 MEAN = (103.939, 116.779, 123.68)  # data_loaders.py:30, applied in RGB channel order as the reference does
@@ -234,8 +235,8 @@ def make_gt_maps(polys, tags, size, device, shrink_ratio=0.4, thresh_min=0.3, th
     scale = float(np.float32(thresh_max - thresh_min))
     ptr = [a.data_ptr() if a.numel() else None for a in args]
     ptr[3] = args[3].data_ptr()
-    check(lib().dbn_gt_maps(*ptr, N, len(meta), S, max_v, max_o, scale, float(np.float32(thresh_min)), out.data_ptr(),
-                            torch.cuda.current_stream(out.device).cuda_stream), 'gt_maps')
+    check(lib().dbn_gt_maps(*ptr, N, len(meta), S, max_v, max_o, scale, float(np.float32(thresh_min)), out.data_ptr(), stream(out.device)),
+          'gt_maps')
     return out
 
 
@@ -248,8 +249,7 @@ def normalize_images(u8, mean=MEAN):
     N, H, W, _ = u8.shape
     out = torch.empty((N, 3, H, W), device=u8.device, dtype=torch.float32)
     m = [float(np.float32(v)) for v in mean]
-    check(lib().dbn_normalize_u8(u8.data_ptr(), N, H, W, m[0], m[1], m[2], out.data_ptr(),
-                                 torch.cuda.current_stream(u8.device).cuda_stream), 'normalize_u8')
+    check(lib().dbn_normalize_u8(u8.data_ptr(), N, H, W, m[0], m[1], m[2], out.data_ptr(), stream(u8.device)), 'normalize_u8')
     return out
 
 

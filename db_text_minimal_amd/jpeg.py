@@ -45,6 +45,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
+from .packed import DecodedBatch, DecodeError, check_bytes, cuda_device, flat_u8, image_offsets, offsets, on_device, pin_default, polys_tags, stream, upload
 
 _DESC, _INFO = 24, 24
 _D_COEF, _D_W, _D_H, _D_NC, _D_OUT, _D_QT, _D_COMP, _D_STATUS = 0, 1, 2, 3, 4, 5, 6, 22
@@ -65,16 +66,9 @@ MULTISCAN_REASONS = {14: 'scan script incomplete at the end of the image, or lon
 _REFUSED = (3, 4, 5, 6, 7, 8, 9, 14)  # valid JPEG kinds this decoder does not take (another decoder can)
 
 
-def _reason(code):
-    return REASONS.get(code) or MULTISCAN_REASONS.get(code)
-
-
-class JpegError(ValueError):
+class JpegError(DecodeError):
     """a stream that was not decoded: .code is the status of include/dbnet_hip.h, .index the image's place in its batch"""
-
-    def __init__(self, code, index=None):
-        self.code, self.index, self.reason = int(code), index, _reason(int(code)) or 'status %d' % code
-        ValueError.__init__(self, self.reason if index is None else 'image %d: %s' % (index, self.reason))
+    reasons, refused = {**REASONS, **MULTISCAN_REASONS}, _REFUSED
 
 
 class UnsupportedJpeg(JpegError):
@@ -85,8 +79,7 @@ class CorruptJpeg(JpegError):
     """not a JPEG, or one that is truncated or damaged"""
 
 
-def _error(code, index=None):
-    return (UnsupportedJpeg if code in _REFUSED else CorruptJpeg)(code, index)
+JpegError.unsupported, JpegError.corrupt = UnsupportedJpeg, CorruptJpeg
 
 
 def _bytes_view(data):
@@ -98,53 +91,22 @@ def _concat_streams(datas, pin):
     """byte strings -> (uint8 tensor that holds them end to end, pinned if asked, one byte long when they are empty; int64
     offsets [N + 1])"""
     views = [_bytes_view(d) for d in datas]
-    offs = np.zeros(len(views) + 1, np.int64)
-    offs[1:] = np.cumsum([v.size for v in views])
+    offs = offsets([v.size for v in views])
     blob = torch.empty(max(int(offs[-1]), 1), dtype=torch.uint8, pin_memory=bool(pin))
     if offs[-1]:
         np.concatenate(views, out=blob.numpy()[:int(offs[-1])])
     return blob, offs
 
 
-def _pin(pin):
-    """pin=None: when a GPU is visible and this is not a DataLoader worker (a loader's pin_memory=True pins there)"""
-    return bool(torch.utils.data.get_worker_info() is None and torch.cuda.is_available() if pin is None else pin)
-
-
-def _cuda_device(who, device, default=None):
-    """`device`, else `default`, else the current GPU, as a cuda device with an index; `who`: the caller's name for the error"""
-    dev = torch.device(device) if device is not None else default
-    if dev is not None and dev.type != 'cuda':
-        raise ValueError('%s runs on a GPU device, not %s' % (who, dev))
-    return dev if dev is not None and dev.index is not None else torch.device('cuda', torch.cuda.current_device())
-
-
-def _polys_tags(items):
-    """items (_, polys, tags) -> (per-image lists of fp64 [V, 2] polygons, per-image tag lists)"""
-    polys = [[np.asarray(p, dtype=np.float64).reshape(-1, 2) for p in b[1]] for b in items]
-    tags = [list(b[2]) if b[2] is not None else [None] * len(b[1]) for b in items]
-    return polys, tags
-
-
-class _JpegBatch:
-    """what a batch's results share, from `desc` and `status`"""
-
-    @property
-    def shapes(self):
-        return [(int(d[_D_H]), int(d[_D_W])) if s == 0 else (0, 0) for d, s in zip(self.desc, self.status)]
+class _JpegBatch(DecodedBatch):
+    """what a batch's results share, from `desc` and `status`; errors(): for JpegStreams the ones the headers give"""
+    error, _hw = JpegError, (_D_H, _D_W)
 
     @property
     def oriented_shapes(self):
         """`shapes` as they are once the Exif orientation is applied: (W, H) for tags 5 .. 8"""
         o = getattr(self, 'orientation', None)
         return [(w, h) if o is not None and 5 <= int(o[i]) <= 8 else (h, w) for i, (h, w) in enumerate(self.shapes)]
-
-    def __len__(self):
-        return len(self.status)
-
-    def errors(self):
-        """per image None or the JpegError that describes why it was not decoded (for JpegStreams: the one its header gives)"""
-        return [None if s == 0 else _error(int(s), i) for i, s in enumerate(self.status)]
 
 
 def jpeg_info(data, multiscan=False):
@@ -164,7 +126,7 @@ def jpeg_info(data, multiscan=False):
     return dict(width=int(out[1]), height=int(out[2]), components=nc, sampling=[(int(out[6 + 2 * c]), int(out[7 + 2 * c])) for c in range(min(nc, 4))],
                 restart_interval=int(out[4]), orientation=int(out[5]), process={0: 'baseline', 1: 'extended', 2: 'progressive'}.get(int(out[14])),
                 jfif=bool(out[16]), adobe_transform=None if out[17] < 0 else int(out[17]), precision=int(out[18]), status=st,
-                supported=st == 0, reason=None if st == 0 else _reason(st), coefficients=int(out[15]), **more)
+                supported=st == 0, reason=None if st == 0 else JpegError.reasons.get(st), coefficients=int(out[15]), **more)
 
 
 class JpegCoefficients(_JpegBatch):
@@ -213,7 +175,7 @@ def entropy_decode(datas, threads=MAX_THREADS, pin=None, multiscan=False):
     total = int(L.dbn_jpeg_coef_elems_ex(blob.data_ptr(), offs.ctypes.data, N, flags, None))
     if total < 0:
         raise RuntimeError('libdbnet_hip: jpeg_coef_elems failed')
-    coef = torch.empty(max(total, 1), dtype=torch.int16, pin_memory=_pin(pin))
+    coef = torch.empty(max(total, 1), dtype=torch.int16, pin_memory=pin_default(pin))
     desc = np.zeros((N, _DESC), np.int64)
     qtabs = np.zeros((N, 3, 64), np.uint16)
     status = np.zeros(N, np.int32)
@@ -263,24 +225,20 @@ def tile_table(desc, status, orientation):
     return np.concatenate(tt) if tt else np.zeros((0, 4), np.int32)
 
 
-def _up(a, dev):
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t.pin_memory() if torch.cuda.is_available() else t).to(dev, non_blocking=True)
-
-
 def decode_coefficients(obj, device=None, orient=False):
     """Device half: JpegCoefficients -> (packed uint8 device tensor, shapes), on the current stream of `device`, no host
     sync.  Images whose status is not 0 take no bytes and have shape (0, 0) (see obj.errors()).  orient=True: an image whose
     obj.orientation is 2 .. 8 is written turned as cv2.imread turns it (a tiled kernel of its own, in the same call), and
     the shapes returned are obj.oriented_shapes."""
-    dev = _cuda_device('decode_coefficients', device)
+    dev = cuda_device('decode_coefficients', device)
     tags = np.zeros(len(obj), np.int32)
     if orient and obj.orientation is not None:
         tags = np.where(np.asarray(obj.status) == 0, np.asarray(obj.orientation, np.int32), 0).astype(np.int32)
         tags[(tags < 2) | (tags > 8)] = 0
     turned = bool(tags.any())
     shapes = obj.oriented_shapes if turned else obj.shapes
-    out_bytes = int(sum(h * w * 3 for h, w in shapes))
+    out_off = image_offsets(shapes)
+    out_bytes = int(out_off[-1])
     out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
     if out_bytes == 0:
         return out, shapes
@@ -288,30 +246,33 @@ def decode_coefficients(obj, device=None, orient=False):
     if turned:
         tb, tt = tb[tags[tb[:, 0]] == 0], tile_table(obj.desc, obj.status, tags)
     hdesc = obj.desc.copy()  # pixels of the decoded images only, packed: an image whose scan failed gives its slot up
-    hdesc[:, _D_OUT] = np.concatenate([[0], np.cumsum([h * w * 3 for h, w in shapes])[:-1]])
-    with torch.cuda.device(dev):
+    hdesc[:, _D_OUT] = out_off[:-1]
+    with on_device(dev) as sh:
         if obj.ready is not None:  # coefficients still on their way from forward_coefficients' stream
             torch.cuda.current_stream(dev).wait_event(obj.ready)
         coef = obj.coef.to(dev, non_blocking=True)
-        desc, qt, a, b = _up(hdesc, dev), _up(obj.qtabs.view(np.int16), dev), _up(ta, dev), _up(tb, dev)
+        desc, qt, a, b = upload(hdesc, dev), upload(obj.qtabs.view(np.int16), dev), upload(ta, dev), upload(tb, dev)
         planes = torch.empty(coef.numel(), dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         if turned:
-            o, t = _up(tags, dev), _up(tt, dev)
+            o, t = upload(tags, dev), upload(tt, dev)
             check(lib().dbn_jpeg_pixels_ex(coef.data_ptr(), coef.numel(), desc.data_ptr(), qt.data_ptr(), len(obj), a.data_ptr(), len(ta),
                                            b.data_ptr() if len(tb) else None, len(tb), o.data_ptr(), t.data_ptr(), len(tt), planes.data_ptr(),
-                                           out.data_ptr(), out_bytes, stream), 'jpeg_pixels')
+                                           out.data_ptr(), out_bytes, sh), 'jpeg_pixels')
         else:
             check(lib().dbn_jpeg_pixels(coef.data_ptr(), coef.numel(), desc.data_ptr(), qt.data_ptr(), len(obj), a.data_ptr(), len(ta), b.data_ptr(),
-                                        len(tb), planes.data_ptr(), out.data_ptr(), out_bytes, stream), 'jpeg_pixels')
+                                        len(tb), planes.data_ptr(), out.data_ptr(), out_bytes, sh), 'jpeg_pixels')
     return out, shapes
 
 
 def _pil_rgb(data):
+    """the PIL fallback's decode of a refused stream -> uint8 [H, W, 3] array (tests patch it under this name)"""
     import io
 
     from PIL import Image
     return np.ascontiguousarray(np.asarray(Image.open(io.BytesIO(bytes(data))).convert('RGB')))
+
+
+pil_rgb = _pil_rgb  # the name png imports it by
 
 
 def orient_array(a, tag):
@@ -340,8 +301,7 @@ def splice_images(packed, shapes, spliced):
             parts.append(packed[o:o + h * w * 3])
             out_shapes.append((h, w))
             o += h * w * 3
-    if o != packed.numel():
-        raise ValueError('packed holds %d bytes, the shapes need %d' % (packed.numel(), o))
+    check_bytes(packed.numel(), o)
     return torch.cat(parts), out_shapes
 
 
@@ -402,21 +362,15 @@ def jpeg_collate(items):
     """collate_fn for items (jpeg bytes, polys, tags): the host half of the decode, here (in the DataLoader worker) ->
     (JpegCoefficients, shapes, per-image lists of fp64 [V, 2] polygons, per-image tag lists); DeviceBatches.convert runs the
     device half.  A stream that cannot be decoded raises (UnsupportedJpeg / CorruptJpeg)."""
-    obj = entropy_decode([b[0] for b in items], threads=min(len(items), MAX_THREADS))
-    for e in obj.errors():
-        if e is not None:
-            raise e
-    return (obj, obj.shapes) + _polys_tags(items)
+    return jpeg_multiscan_collate(items, False)
 
 
 def jpeg_multiscan_collate(items, multiscan=True):
     """jpeg_collate that takes progressive and multi-scan streams as well (entropy_decode(..., multiscan=True)); the keyword
     is there for functools.partial"""
     obj = entropy_decode([b[0] for b in items], threads=min(len(items), MAX_THREADS), multiscan=multiscan)
-    for e in obj.errors():
-        if e is not None:
-            raise e
-    return (obj, obj.shapes) + _polys_tags(items)
+    obj.raise_errors()
+    return (obj, obj.shapes) + polys_tags(items)
 
 
 # ---- entropy decoding on the device ------------------------------------------------------------------------------------
@@ -456,7 +410,7 @@ def parse_streams(datas, pin=None):
     """Host half of the device entropy stage: the headers of the JPEG byte strings `datas` (the kinds and status codes of
     entropy_decode) and their scans cut into restart intervals at the markers -> JpegStreams.  No bit of the entropy data
     is read.  Runs anywhere, e.g. in a DataLoader worker.  pin: as entropy_decode."""
-    blob, offs = _concat_streams(datas, _pin(pin))
+    blob, offs = _concat_streams(datas, pin_default(pin))
     N = len(offs) - 1
     if N == 0:
         raise ValueError('parse_streams needs at least one stream')
@@ -485,11 +439,10 @@ def _dhuff_launch(st, dev, rounds, coef, ws):
     blob = st.blob.to(dev, non_blocking=True)
     desc = st.desc.copy()
     desc[:, _D_STATUS] = st.status
-    arrs = [_up(a, dev) for a in (desc, st.tables, st.info, st.segments if len(st.segments) else np.zeros((1, _SEG), np.int64), st.sub_base,
+    arrs = [upload(a, dev) for a in (desc, st.tables, st.info, st.segments if len(st.segments) else np.zeros((1, _SEG), np.int64), st.sub_base,
                                   st.wgtab if len(st.wgtab) else np.zeros((1, 4), np.int32))]
     check(lib().dbn_jpeg_dhuff(blob.data_ptr(), blob.numel(), *[a.data_ptr() for a in arrs], N, len(st.segments), int(st.sub_base[-1]), len(st.wgtab),
-                               rounds, coef.data_ptr(), st.coef_elems, ws.data_ptr(), ws.numel(), res.data_ptr(),
-                               torch.cuda.current_stream(dev).cuda_stream), 'jpeg_dhuff')
+                               rounds, coef.data_ptr(), st.coef_elems, ws.data_ptr(), ws.numel(), res.data_ptr(), stream(dev)), 'jpeg_dhuff')
     return res.view(rounds + 2, N)
 
 
@@ -504,10 +457,10 @@ def entropy_decode_device(streams, device=None, max_rounds=None):
     rounds = DHUFF_ROUNDS if max_rounds is None else int(max_rounds)
     if not 0 <= rounds <= 64:
         raise ValueError('max_rounds is 0 .. 64, got %r' % (max_rounds, ))
-    dev = _cuda_device('entropy_decode_device', device)
+    dev = cuda_device('entropy_decode_device', device)
     N = len(st)
     status, desc = st.status.copy(), st.desc.copy()
-    with torch.cuda.device(dev):
+    with on_device(dev):
         coef = torch.empty(max(st.coef_elems, 1), dtype=torch.int16, device=dev)
         ws = torch.empty(max(dhuff_workspace_bytes(st), 8), dtype=torch.uint8, device=dev)
         res = _dhuff_launch(st, dev, rounds, coef, ws).cpu().numpy()  # the one wait
@@ -531,10 +484,8 @@ def jpeg_stream_collate(items):
     tags); DeviceBatches.convert runs the Huffman stage and the pixel stage on the device.  A header that cannot be decoded
     raises here; a damaged scan raises in convert."""
     obj = parse_streams([b[0] for b in items])
-    for e in obj.errors():
-        if e is not None:
-            raise e
-    return (obj, obj.shapes) + _polys_tags(items)
+    obj.raise_errors()
+    return (obj, obj.shapes) + polys_tags(items)
 
 
 # ---- encode ----------------------------------------------------------------------------------------------------------
@@ -582,15 +533,8 @@ def _tables(quality, qtables):
     return t.astype(np.uint16)
 
 
-def _flat_u8(a, dev):
-    t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
-        raise ValueError('images must be uint8 tensors or arrays')
-    return t.contiguous().view(-1).to(dev, non_blocking=True)
-
-
-def _encode_inputs(images, shapes, dev):
-    """-> (uint8 1-D device tensor, [(byte offset, H, W, components)])"""
+def encode_inputs(images, shapes, dev):
+    """the layouts the encoders take -> (uint8 1-D device tensor, [(byte offset, H, W, components)])"""
     if shapes is not None:
         if not (isinstance(images, torch.Tensor) and images.dim() == 1):
             raise ValueError('with shapes, images is the packed 1-D uint8 batch')
@@ -598,16 +542,15 @@ def _encode_inputs(images, shapes, dev):
         for h, w in shapes:
             items.append((o, int(h), int(w), 3))
             o += int(h) * int(w) * 3
-        if o != images.numel():
-            raise ValueError('packed holds %d bytes, the shapes need %d' % (images.numel(), o))
-        flat = _flat_u8(images, dev)
+        check_bytes(images.numel(), o)
+        flat = flat_u8(images, dev)
     elif isinstance(images, (list, tuple)):
         parts, items, o = [], [], 0
         for a in images:
             if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
                 raise ValueError('an image of a list is uint8 [H, W] or [H, W, 3], got %s' % (tuple(a.shape), ))
             nc = 1 if a.ndim == 2 else 3
-            parts.append(_flat_u8(a, dev))
+            parts.append(flat_u8(a, dev))
             items.append((o, int(a.shape[0]), int(a.shape[1]), nc))
             o += parts[-1].numel()
         if not parts:
@@ -629,7 +572,7 @@ def _encode_inputs(images, shapes, dev):
         if n < 1:
             raise ValueError('no images')
         items = [(i * h * w * nc, h, w, nc) for i in range(n)]
-        flat = _flat_u8(a, dev)
+        flat = flat_u8(a, dev)
     for _, h, w, _ in items:
         if not (1 <= h <= 65535 and 1 <= w <= 65535):
             raise ValueError('a JPEG image is 1 .. 65535 pixels on a side, got %d x %d' % (h, w))
@@ -694,23 +637,22 @@ def forward_coefficients(images, shapes=None, quality=75, subsampling='420', qta
     host_copy=False: the coefficients stay on the device (`coef.is_cuda`; no pinned buffer, no copy), for
     entropy_encode_device and decode_coefficients."""
     tables = _tables(quality, qtables)
-    dev = _cuda_device('forward_coefficients', device, images.device if isinstance(images, torch.Tensor) and images.is_cuda else None)
-    with torch.cuda.device(dev):
-        flat, items = _encode_inputs(images, shapes, dev)
+    dev = cuda_device('forward_coefficients', device, images)
+    with on_device(dev) as sh:
+        flat, items = encode_inputs(images, shapes, dev)
         hdesc, qtabs, total, tp, tf = forward_plan(items, subsampling, tables)
-        desc, qt, a, b = _up(hdesc, dev), _up(qtabs.view(np.int16), dev), _up(tp, dev), _up(tf, dev)
+        desc, qt, a, b = upload(hdesc, dev), upload(qtabs.view(np.int16), dev), upload(tp, dev), upload(tf, dev)
         coef = torch.empty(total, dtype=torch.int16, device=dev)
         planes = torch.empty(total, dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev)
         check(lib().dbn_jpeg_forward(flat.data_ptr(), flat.numel(), desc.data_ptr(), qt.data_ptr(), len(items), a.data_ptr(), len(tp),
-                                     b.data_ptr(), len(tf), planes.data_ptr(), coef.data_ptr(), total, stream.cuda_stream), 'jpeg_forward')
+                                     b.data_ptr(), len(tf), planes.data_ptr(), coef.data_ptr(), total, sh), 'jpeg_forward')
         if host_copy:
             host = torch.empty(total, dtype=torch.int16, pin_memory=True)
             host.copy_(coef, non_blocking=True)
         else:
             host = coef
         ready = torch.cuda.Event()
-        ready.record(stream)
+        ready.record(torch.cuda.current_stream(dev))
     hdesc[:, _D_OUT] = np.cumsum(hdesc[:, _D_W] * hdesc[:, _D_H] * 3) - hdesc[:, _D_W] * hdesc[:, _D_H] * 3  # as entropy_decode leaves it
     obj = JpegCoefficients(host, hdesc, qtabs, np.zeros(len(items), np.int32))
     obj.ready = ready
@@ -762,7 +704,7 @@ def entropy_encode_device(obj, restart_interval=0, optimize=False, errors='raise
     qtabs = np.ascontiguousarray(obj.qtabs, np.uint16)
     if obj.coef.dtype != torch.int16 or desc.shape != (N, _DESC) or qtabs.shape != (N, 3, 64):
         raise ValueError('not the layout of JpegCoefficients')
-    dev = _cuda_device('entropy_encode_device', device, obj.coef.device if obj.coef.is_cuda else None)
+    dev = cuda_device('entropy_encode_device', device, obj.coef)
     L = lib()
     blk, ivl = np.zeros(N + 1, np.int64), np.zeros(N + 1, np.int64)
     status, sizes = np.zeros(N, np.int32), np.zeros(2, np.int64)
@@ -772,28 +714,27 @@ def entropy_encode_device(obj, restart_interval=0, optimize=False, errors='raise
     specs, codes = np.zeros((N if optimize else 1, 4, 273), np.uint16), np.zeros((N if optimize else 1, 4, 256), np.uint32)
     scans = [b''] * N
     if total:
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev)
+        with on_device(dev) as sh:
             if obj.ready is not None:
-                stream.wait_event(obj.ready)
+                torch.cuda.current_stream(dev).wait_event(obj.ready)
             coef = obj.coef.contiguous().to(dev, non_blocking=True)
-            ddesc, dblk, divl = _up(desc, dev), _up(blk, dev), _up(ivl, dev)
+            ddesc, dblk, divl = upload(desc, dev), upload(blk, dev), upload(ivl, dev)
             res = torch.full((2 * N + 1, ), -1, dtype=torch.int64, device=dev)
             if optimize:
                 hist = torch.empty((N, 4, 256), dtype=torch.int32, device=dev)
                 check(L.dbn_jpeg_huff_hist(coef.data_ptr(), coef.numel(), ddesc.data_ptr(), N, dblk.data_ptr(), total, ri, hist.data_ptr(),
-                                           res.data_ptr(), stream.cuda_stream), 'jpeg_huff_hist')
+                                           res.data_ptr(), sh), 'jpeg_huff_hist')
                 hhist = hist.cpu().numpy().view(np.uint32)  # the one host step between launches
                 check(L.dbn_jpeg_huff_tables(hhist.ctypes.data, desc.ctypes.data, N, status.ctypes.data, specs.ctypes.data, codes.ctypes.data,
                                              MAX_THREADS), 'jpeg_huff_tables')
             else:
                 check(L.dbn_jpeg_huff_annex_k(specs.ctypes.data, codes.ctypes.data), 'jpeg_huff_annex_k')
-            dcodes = _up(codes.view(np.int32), dev)
+            dcodes = upload(codes.view(np.int32), dev)
             ws = torch.empty(int(sizes[0]), dtype=torch.uint8, device=dev)
             out = torch.empty(int(sizes[1]), dtype=torch.uint8, device=dev)
             check(L.dbn_jpeg_huff_code(coef.data_ptr(), coef.numel(), ddesc.data_ptr(), N, dblk.data_ptr(), divl.data_ptr(), total, intervals, ri,
                                        dcodes.data_ptr(), int(bool(optimize)), ws.data_ptr(), ws.numel(), out.data_ptr(), out.numel(),
-                                       res.data_ptr(), stream.cuda_stream), 'jpeg_huff_code')
+                                       res.data_ptr(), sh), 'jpeg_huff_code')
             hres = res.cpu().numpy().view(np.uint64)  # the one wait: error keys and offsets
             offs = hres[N:].astype(np.int64)
             if not (np.all(np.diff(offs) >= 0) and 0 <= offs[0] and offs[N] <= out.numel()):
@@ -837,8 +778,7 @@ def entropy_encode(obj, restart_interval=0, threads=MAX_THREADS, errors='raise',
     total = int(L.dbn_jpeg_encode_bound(desc.ctypes.data, N, ri, per.ctypes.data))
     if total < 0:
         raise RuntimeError('libdbnet_hip: jpeg_encode_bound failed')
-    offs = np.zeros(N + 1, np.int64)
-    offs[1:] = np.cumsum(per)
+    offs = offsets(per)
     out = np.empty(max(total, 1), np.uint8)  # the worst case; only the pages a stream reaches are ever touched
     lens, status = np.zeros(N, np.int64), np.zeros(N, np.int32)
     check(L.dbn_jpeg_encode_batch_opt(coef.data_ptr(), coef.numel(), desc.ctypes.data, qtabs.ctypes.data, N, ri, out.ctypes.data, total,

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
-from .jpeg import _up
+from .packed import check_bytes, flat_u8, on_device, upload
 
 OPS = ('brightness', 'contrast', 'saturation', 'hue')
 _CODE = {name: k + 1 for k, name in enumerate(OPS)}
@@ -115,14 +115,6 @@ def plan_records(shapes, plans):
 
 
 # ---- device --------------------------------------------------------------------------------------------------------
-def _flat_u8(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError('%s must be a tensor on a GPU device (there is no host path)' % what)
-    if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
-        raise ValueError('%s must be a flat contiguous uint8 tensor' % what)
-    return t
-
-
 def color_jitter_images(packed_u8, shapes, plans, out=None):
     """Packed uint8 RGB images on the device (image_collate's layout: [H, W, 3] each, end to end) -> the packed uint8 tensor
     after each image's plan.  Two launches for the whole batch on the current stream (one when no plan holds contrast), no
@@ -130,22 +122,20 @@ def color_jitter_images(packed_u8, shapes, plans, out=None):
     without being it is refused."""
     shapes = [(int(h), int(w)) for h, w in shapes]
     desc = plan_records(shapes, plans)
-    src = _flat_u8(packed_u8, 'packed_u8')
+    src = flat_u8(packed_u8, what='packed_u8')
     need = int(sum(3 * h * w for h, w in shapes))
-    if src.numel() != need:
-        raise ValueError('packed_u8 holds %d bytes, the shapes need %d' % (src.numel(), need))
-    dst = torch.empty_like(src) if out is None else _flat_u8(out, 'out')
+    check_bytes(src.numel(), need, 'packed_u8 holds')
+    dst = torch.empty_like(src) if out is None else flat_u8(out, what='out')
     if dst.numel() != need or dst.device != src.device:
         raise ValueError('out must hold %d bytes on %s' % (need, src.device))
     a, b = src.data_ptr(), dst.data_ptr()
     if a != b and a < b + need and b < a + need:  # a shifted view of the input: lanes would read what others have written
         raise ValueError('out must be the input itself or must not overlap it')
     N, dev = len(shapes), src.device
-    with torch.cuda.device(dev):
+    with on_device(dev) as stream:
         contrast = any(name == 'contrast' for plan in plans for name, _ in plan)
         sums = torch.empty(N, dtype=torch.int64, device=dev) if contrast else None
-        d = _up(desc, dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        d = upload(desc, dev)
         check(lib().dbn_color_jitter_u8(src.data_ptr(), dst.data_ptr(), need, desc.ctypes.data, d.data_ptr(), N,
                                         sums.data_ptr() if contrast else None, stream), 'color_jitter_u8')
     return dst

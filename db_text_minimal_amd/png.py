@@ -39,7 +39,9 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
-from .jpeg import MAX_THREADS, _cuda_device, _encode_inputs, _pil_rgb, _pin, _polys_tags, _up, splice_images
+from .jpeg import MAX_THREADS, decode_jpeg_batch, encode_inputs, splice_images
+from .jpeg import pil_rgb as _pil_rgb  # called through this module's name, where tests patch it
+from .packed import MAX_SIDE, DecodedBatch, DecodeError, cuda_device, image_offsets, on_device, pin_default, polys_tags, upload
 
 SIGNATURE = b'\x89PNG\r\n\x1a\n'
 _DESC = 32  # int64 fields per image (include/dbnet_hip.h)
@@ -48,7 +50,7 @@ _CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
 _DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}
 _ADAM7 = ((0, 0, 8, 8), (4, 0, 8, 8), (0, 4, 4, 8), (2, 0, 4, 4), (0, 2, 2, 4), (1, 0, 2, 2), (0, 1, 1, 2))  # x0, y0, dx, dy of passes 1 .. 7
 UNFILTER_ROWS, UNFILTER_CHUNK = 256, 16  # rows of a band, bytes of a chunk (csrc/png.hip)
-MAX_SIDE, MAX_RAW = 65535, (1 << 31) - 1
+MAX_RAW = (1 << 31) - 1
 _BLOB_PAD = 32  # bytes allocated past the blob's end: the unfilter kernel reads whole aligned words
 
 REASONS = {
@@ -61,12 +63,9 @@ REASONS = {
 _REFUSED = (20, 21)
 
 
-class PngError(ValueError):
+class PngError(DecodeError):
     """a file that was not decoded: .code is the status (REASONS), .index the image's place in its batch"""
-
-    def __init__(self, code, index=None):
-        self.code, self.index, self.reason = int(code), index, REASONS.get(int(code), 'status %d' % code)
-        ValueError.__init__(self, self.reason if index is None else 'image %d: %s' % (index, self.reason))
+    reasons, refused = REASONS, _REFUSED
 
 
 class UnsupportedPng(PngError):
@@ -77,8 +76,7 @@ class CorruptPng(PngError):
     """not a PNG, or one that is truncated or damaged"""
 
 
-def _error(code, index=None):
-    return (UnsupportedPng if code in _REFUSED else CorruptPng)(code, index)
+PngError.unsupported, PngError.corrupt = UnsupportedPng, CorruptPng
 
 
 class _Fail(Exception):
@@ -203,28 +201,18 @@ def _inflate_one(data):
         return e.code, hdr, None, b''
 
 
-class PngScanlines:
+class PngScanlines(DecodedBatch):
     """The host half's result for a batch: `blob` uint8 tensor, the still filtered scanlines of every image end to end (pinned when
     asked for; 32 spare bytes behind them), `blob_len` their count, `desc` int64 [N, 32] (width, height, bit depth, colour type,
     interlace, output offset, palette entries, status, and per sub-image the offsets in the blob and in the device workspace:
     include/dbnet_hip.h), `palettes` uint8 [N, 256, 3], `status` int32 [N] (0: inflated), `subs` int32 [S, 2] (image, sub-image: one
     workgroup each), `raw_bytes` the workspace the device half needs.  Picklable; pin_memory() makes it what a DataLoader with
     pin_memory=True hands on."""
+    error, _hw = PngError, (_D_H, _D_W)
 
     def __init__(self, blob, blob_len, desc, palettes, status, subs, raw_bytes):
         self.blob, self.blob_len, self.desc, self.palettes, self.status = blob, int(blob_len), desc, palettes, status
         self.subs, self.raw_bytes = subs, int(raw_bytes)
-
-    @property
-    def shapes(self):
-        return [(int(d[_D_H]), int(d[_D_W])) if s == 0 else (0, 0) for d, s in zip(self.desc, self.status)]
-
-    def __len__(self):
-        return len(self.status)
-
-    def errors(self):
-        """per image None or the PngError that says why it was not decoded"""
-        return [None if s == 0 else _error(int(s), i) for i, s in enumerate(self.status)]
 
     def pin_memory(self):
         if not self.blob.is_pinned():
@@ -267,7 +255,7 @@ def inflate_png(datas, threads=MAX_THREADS, pin=None):
             src += ph * (rb + 1)
             raw += ph * (-(-rb // UNFILTER_CHUNK) * UNFILTER_CHUNK)
         out += h * w * 3
-    blob = torch.empty(src + _BLOB_PAD, dtype=torch.uint8, pin_memory=_pin(pin))
+    blob = torch.empty(src + _BLOB_PAD, dtype=torch.uint8, pin_memory=pin_default(pin))
     view = blob.numpy()
     view[src:] = 0
     o = 0
@@ -283,22 +271,21 @@ def unfilter_png(obj, device=None, _raw=None):
     """Device half: PngScanlines -> (packed uint8 device tensor, shapes), on the current stream of `device`, no host sync: one
     upload of the blob and the tables, the unfilter launch (one workgroup per sub-image), the pixel launch.  Images whose status
     is not 0 take no bytes and have shape (0, 0) (see obj.errors()).  _raw: a workspace of obj.raw_bytes to use (tests)."""
-    dev = _cuda_device('unfilter_png', device)
+    dev = cuda_device('unfilter_png', device)
     shapes = obj.shapes
-    out_bytes = int(sum(h * w * 3 for h, w in shapes))
+    out_bytes = int(image_offsets(shapes)[-1])
     out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
     if out_bytes == 0:
         return out, shapes
     hdesc, hsubs = np.ascontiguousarray(obj.desc, np.int64), np.ascontiguousarray(obj.subs, np.int32)
     L = lib()
     check(L.dbn_png_check(hdesc.ctypes.data, len(obj), hsubs.ctypes.data, len(hsubs), obj.blob_len, obj.raw_bytes, out_bytes), 'png_check')
-    with torch.cuda.device(dev):
+    with on_device(dev) as stream:
         blob = obj.blob.to(dev, non_blocking=True)
-        desc, subs, pal = _up(hdesc, dev), _up(hsubs, dev), _up(obj.palettes, dev)
+        desc, subs, pal = upload(hdesc, dev), upload(hsubs, dev), upload(obj.palettes, dev)
         raw = torch.empty(obj.raw_bytes, dtype=torch.uint8, device=dev) if _raw is None else _raw
         if raw.numel() < obj.raw_bytes or raw.dtype != torch.uint8 or raw.device != blob.device:
             raise ValueError('the workspace is %d uint8 on the device' % obj.raw_bytes)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         check(L.dbn_png_unfilter(blob.data_ptr(), obj.blob_len, blob.numel(), hdesc.ctypes.data, desc.data_ptr(), len(obj), hsubs.ctypes.data,
                                  subs.data_ptr(), len(hsubs), raw.data_ptr(), obj.raw_bytes, out_bytes, stream), 'png_unfilter')
         check(L.dbn_png_pixels(raw.data_ptr(), obj.raw_bytes, hdesc.ctypes.data, desc.data_ptr(), pal.data_ptr(), len(obj), obj.blob_len,
@@ -349,10 +336,8 @@ def png_collate(items):
     (PngScanlines, shapes, per-image lists of fp64 [V, 2] polygons, per-image tag lists); DeviceBatches.convert runs the device
     half.  A file that cannot be decoded raises (UnsupportedPng / CorruptPng)."""
     obj = inflate_png([b[0] for b in items], threads=min(len(items), MAX_THREADS), pin=None)
-    for e in obj.errors():
-        if e is not None:
-            raise e
-    return (obj, obj.shapes) + _polys_tags(items)
+    obj.raise_errors()
+    return (obj, obj.shapes) + polys_tags(items)
 
 
 def decode_image_batch(datas, device=None, **kw):
@@ -360,7 +345,6 @@ def decode_image_batch(datas, device=None, **kw):
     (packed, shapes), or (packed, shapes, errs) with errors='report'.  The first bytes decide: FF D8 is JPEG and goes to
     decode_jpeg_batch, everything else to decode_png_batch (which names what is not a PNG); each decoder runs once.  kw:
     threads, fallback, errors for both; entropy, multiscan, orient for the JPEGs.  Error indices are the callers'."""
-    from .jpeg import decode_jpeg_batch
     datas = list(datas)
     if not datas:
         raise ValueError('decode_image_batch needs at least one stream')
@@ -401,10 +385,10 @@ def _filter_arg(filter):
 def _filter_launch(images, shapes, filter, device):
     """-> (uint8 device tensor of every image's filtered rows, [(offset, H, row bytes + 1, channels, W)])"""
     f = _filter_arg(filter)
-    dev = _cuda_device('filter_png_rows', device, images.device if isinstance(images, torch.Tensor) and images.is_cuda else None)
-    with torch.cuda.device(dev):
+    dev = cuda_device('filter_png_rows', device, images)
+    with on_device(dev) as stream:
         try:
-            flat, items = _encode_inputs(images, shapes, dev)  # the layouts, and the 65535-pixel limit, are the JPEG encoder's
+            flat, items = encode_inputs(images, shapes, dev)  # the layouts, and the 65535-pixel limit, are the JPEG encoder's
         except ValueError as e:
             raise ValueError(str(e).replace('a JPEG image', 'a PNG image written here')) from None
         hdesc = np.zeros((len(items), 8), np.int64)
@@ -416,9 +400,9 @@ def _filter_launch(images, shapes, filter, device):
             o += h * (w * nc + 1)
             rows += h
         out = torch.empty(o, dtype=torch.uint8, device=dev)
-        desc = _up(hdesc, dev)
-        check(lib().dbn_png_filter_rows(flat.data_ptr(), flat.numel(), hdesc.ctypes.data, desc.data_ptr(), len(items), f, out.data_ptr(), o,
-                                        torch.cuda.current_stream(dev).cuda_stream), 'png_filter_rows')
+        desc = upload(hdesc, dev)
+        check(lib().dbn_png_filter_rows(flat.data_ptr(), flat.numel(), hdesc.ctypes.data, desc.data_ptr(), len(items), f, out.data_ptr(), o, stream),
+              'png_filter_rows')
     return out, layout
 
 

@@ -53,10 +53,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
+from .packed import stream
 
 
 def binarize_u8(preds, thresh=0.3):
@@ -64,7 +61,7 @@ def binarize_u8(preds, thresh=0.3):
     assert preds.is_cuda and preds.dtype == torch.float32 and preds.dim() == 4 and preds.is_contiguous()
     N, C, H, W = preds.shape
     out = torch.empty((N, H, W), device=preds.device, dtype=torch.uint8)
-    check(lib().dbn_binarize_u8(preds.data_ptr(), N, C, H, W, float(thresh), out.data_ptr(), _stream(preds)), 'binarize_u8')
+    check(lib().dbn_binarize_u8(preds.data_ptr(), N, C, H, W, float(thresh), out.data_ptr(), stream(preds.device)), 'binarize_u8')
     return out
 
 
@@ -80,7 +77,7 @@ def box_scores(prob_map, boxes):
     bd = b.to(prob_map.device)
     scores = torch.empty(K, device=prob_map.device, dtype=torch.float32)
     H, W = prob_map.shape
-    check(lib().dbn_box_scores(prob_map.data_ptr(), H, W, bd.data_ptr(), K, P, scores.data_ptr(), _stream(prob_map)), 'box_scores')
+    check(lib().dbn_box_scores(prob_map.data_ptr(), H, W, bd.data_ptr(), K, P, scores.data_ptr(), stream(prob_map.device)), 'box_scores')
     return scores.cpu().numpy()
 
 
@@ -113,7 +110,7 @@ def detect_records(preds, thresh=0.3, max_candidates=1000, return_labels=False, 
         for t in (ws, labels.view(torch.uint8), out):
             t.fill_(int(prefill))
     check(L.dbn_detect(preds.data_ptr(), N, C, H, W, float(thresh), M, ws.data_ptr(), labels.data_ptr(), out.data_ptr(),
-                       out.data_ptr() + rec_bytes, _stream(preds)), 'detect')
+                       out.data_ptr() + rec_bytes, stream(preds.device)), 'detect')
     host = out.cpu().numpy()
     recs = host[:rec_bytes].view(REC_DTYPE).reshape(N, M)
     counts = host[rec_bytes:].view(np.int32).copy()
@@ -179,7 +176,7 @@ def detect_contours(preds, thresh=0.3, max_candidates=1000, prefill=None):
         for t in (ws, pws, labels.view(torch.uint8), table, verts.view(torch.uint8)):
             t.fill_(int(prefill))
     check(L.dbn_detect_poly(preds.data_ptr(), N, C, H, W, float(thresh), M, ws.data_ptr(), pws.data_ptr(), labels.data_ptr(), table.data_ptr(),
-                            verts.data_ptr(), _stream(preds)), 'detect_poly')
+                            verts.data_ptr(), stream(preds.device)), 'detect_poly')
     host = table.cpu().numpy()
     info = host[o_info:].view(np.int32).copy()
     return dict(recs=host[:o_counts].view(REC_DTYPE).reshape(N, M), counts=host[o_counts:o_nv].view(np.int32).copy(),

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
-from .augment import _stream
+from .packed import on_device
 from .word_crops import SIZE, crop_words, rectify_words
 
 _INT_MAX = 2 ** 31 - 1
@@ -65,8 +65,10 @@ def words_to_input(crops, rgb=False, bgr=False, dtype=torch.float32):
     if K == 0:
         return out
     crops = crops.contiguous()
-    check(lib().dbn_words_to_input(_AT[dtype], crops.data_ptr(), n_px, h * w, int(bool(rgb)), int(bool(bgr)), _table_on(crops.device).data_ptr(),
-                                   out.data_ptr(), _stream(crops.device)), 'words_to_input')
+    table = _table_on(crops.device)
+    with on_device(crops.device) as st:
+        check(lib().dbn_words_to_input(_AT[dtype], crops.data_ptr(), n_px, h * w, int(bool(rgb)), int(bool(bgr)), table.data_ptr(), out.data_ptr(), st),
+              'words_to_input')
     return out
 
 
@@ -113,8 +115,9 @@ def greedy_decode(logits, mode='ctc', lengths=None):
         return codes, count.zero_(), score.fill_(1.0)
     logits = logits.contiguous()
     ws = torch.empty((lib().dbn_greedy_decode_ws_bytes(B, T) // 4, ), device=dev, dtype=torch.int32)
-    check(lib().dbn_greedy_decode(_AT[logits.dtype], logits.data_ptr(), B, T, C, len_ptr, _MODES[mode], ws.data_ptr(), codes.data_ptr(),
-                                  count.data_ptr(), score.data_ptr(), _stream(dev)), 'greedy_decode')
+    with on_device(dev) as st:
+        check(lib().dbn_greedy_decode(_AT[logits.dtype], logits.data_ptr(), B, T, C, len_ptr, _MODES[mode], ws.data_ptr(), codes.data_ptr(),
+                                      count.data_ptr(), score.data_ptr(), st), 'greedy_decode')
     return codes, count, score
 
 

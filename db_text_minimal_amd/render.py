@@ -42,8 +42,8 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
-from .augment import _check_shape, _offsets, _packed, _resize_coef, _stream, _to_device
-from .word_crops import _images
+from .packed import as_images, check_bytes, check_shape, cuda_device, image_offsets, image_table, on_device, packed_on, upload
+from .packed import offsets as _offsets
 
 CMAPS = ('inferno', 'jet')
 _VERT_MAX = 2 ** 20  # |vertex coordinate| of a shape (csrc/render.hip)
@@ -70,24 +70,18 @@ def colormap_table(name):
     return _tables[name]
 
 
-def _call(name, *args):
+def _call(name, dev, *args):
+    """the C entry point `name` on the current stream of `dev`, its handle the last argument"""
     LAUNCH_LOG.append(name)
-    check(getattr(lib(), name)(*args), name)
-
-
-def _device(packed, device):
-    dev = torch.device(device) if device is not None else (packed.device if packed.is_cuda else torch.device('cuda', torch.cuda.current_device()))
-    if dev.type != 'cuda':
-        raise ValueError('rendering runs on a GPU device, not %s' % dev)
-    return dev
+    with on_device(dev) as st:
+        check(getattr(lib(), name)(*args, st), name)
 
 
 def image_views(packed, shapes):
     """per-image uint8 [H, W, 3] views of a packed result"""
-    shapes = [_check_shape(s) for s in shapes]
-    off = _offsets([h * w * 3 for h, w in shapes])
-    if packed.dim() != 1 or packed.numel() != int(off[-1]):
-        raise ValueError('the packed images hold %d bytes, the shapes need %d' % (packed.numel(), int(off[-1])))
+    shapes = [check_shape(s) for s in shapes]
+    off = image_offsets(shapes)
+    check_bytes(packed.numel(), int(off[-1]), 'the packed images hold', packed.dim() == 1)
     return [packed[int(off[n]):int(off[n + 1])].view(h, w, 3) for n, (h, w) in enumerate(shapes)]
 
 
@@ -176,23 +170,22 @@ def draw_outlines(images, shapes_per_image, color=(255, 0, 0), thickness=3, devi
     within thickness / 2 of the segment, exactly; round joins and caps): pixels on the rim may differ from cv2's.
     Returns the packed uint8 device copy with the outlines (image_views splits it).  One copy and one launch on the
     current stream."""
-    packed, shapes = _images(images)
+    packed, shapes = as_images(images)
     c = _color(color)
     if isinstance(thickness, bool) or int(thickness) != thickness or not 1 <= int(thickness) <= 255:
         raise ValueError('thickness must be an integer in 1 .. 255, got %r' % (thickness, ))
     edges = stroke_edges(shapes_per_image, len(shapes))
     if -(-len(edges) // 4) > _INT_MAX:
         raise ValueError('%d edges are too many for one call' % len(edges))
-    dev = _device(packed, device)
-    src = _packed(packed, shapes, dev)
+    dev = cuda_device('rendering', device, packed)
+    src = packed_on(packed, shapes, dev)
     out = torch.empty_like(src)
     if src.numel() == 0:
         return out
-    desc = np.stack([_offsets([h * w * 3 for h, w in shapes])[:-1], [h for h, _ in shapes], [w for _, w in shapes]], 1).astype(np.int64)
-    d = _to_device(desc, dev)
-    e = _to_device(edges, dev) if len(edges) else None
-    _call('dbn_draw_strokes', src.data_ptr(), out.data_ptr(), src.numel(), d.data_ptr(), len(shapes), e.data_ptr() if e is not None else None,
-          len(edges), int(thickness), c[0], c[1], c[2], _stream(dev))
+    d = image_table(shapes, dev)
+    e = upload(edges, dev) if len(edges) else None
+    _call('dbn_draw_strokes', dev, src.data_ptr(), out.data_ptr(), src.numel(), d.data_ptr(), len(shapes), e.data_ptr() if e is not None else None,
+          len(edges), int(thickness), c[0], c[1], c[2])
     return out
 
 
@@ -228,7 +221,7 @@ def overlay_plan(shapes, map_hw, valid_hw=None, vmin=None, vmax=None):
         if not (1 <= vh <= Hm and 1 <= vw <= Wm):
             raise ValueError('valid_hw %d x %d of image %d outside the %d x %d map' % (vh, vw, n, Hm, Wm))
         desc[n] = first[n], H, W, vh, vw
-        coef[n] = _resize_coef(vw, W), _resize_coef(vh, H), lo[n], hi[n]
+        coef[n] = 1. / (float(W) / vw), 1. / (float(H) / vh), lo[n], hi[n]  # cv2.resize: scale = 1. / ((double)dst / src)
     return desc, coef, auto
 
 
@@ -245,7 +238,7 @@ def overlay_heatmap(images, prob, valid_hw=None, cmap='inferno', alpha=0.6, vmin
     uint8 device buffer that already holds the picture to paint over, e.g. the result of draw_outlines: it is painted in
     place and returned, and `images` then only gives the shapes.  Without it the images are read, never written, and a
     new packed buffer is returned.  The blend stands for matplotlib's compositing at figure resolution: unpinned."""
-    packed, shapes = _images(images)
+    packed, shapes = as_images(images)
     N = len(shapes)
     if not (isinstance(prob, torch.Tensor) and prob.is_cuda and prob.dtype == torch.float32 and prob.dim() in (3, 4)):
         raise ValueError('prob must be a float32 device tensor [N, H, W] or [N, C, H, W]')
@@ -264,7 +257,7 @@ def overlay_heatmap(images, prob, valid_hw=None, cmap='inferno', alpha=0.6, vmin
             raise ValueError('out must be a packed uint8 tensor of %d bytes on %s' % (packed.numel(), dev))
         src = out
     else:
-        src = _packed(packed, shapes, dev)
+        src = packed_on(packed, shapes, dev)
         out = torch.empty_like(src)
     n_px = src.numel() // 3
     if -(-n_px // 1024) > _INT_MAX:
@@ -273,15 +266,15 @@ def overlay_heatmap(images, prob, valid_hw=None, cmap='inferno', alpha=0.6, vmin
         return out
     prob = prob.contiguous()
     img_stride = prob.numel() // N
-    d, c = _to_device(desc, dev), _to_device(coef, dev)
-    lut = _to_device((table[:, 0].astype(np.int64) | table[:, 1].astype(np.int64) << 8 | table[:, 2].astype(np.int64) << 16).astype(np.int32), dev)
+    d, c = upload(desc, dev), upload(coef, dev)
+    lut = upload((table[:, 0].astype(np.int64) | table[:, 1].astype(np.int64) << 8 | table[:, 2].astype(np.int64) << 16).astype(np.int32), dev)
     is_bin, thresh = (0, 0.0) if binary is None else (1, float(binary))
     common = (d.data_ptr(), c.data_ptr(), N, n_px, prob.data_ptr(), prob.numel(), img_stride, Wm, is_bin, thresh)
     mm = None
     if auto:
         mm = torch.empty(2 * N, device=dev, dtype=torch.int32)
-        _call('dbn_render_minmax', *common, mm.data_ptr(), _stream(dev))
-    _call('dbn_render_paint', src.data_ptr(), out.data_ptr(), *common, mm.data_ptr() if auto else None, lut.data_ptr(), a, _stream(dev))
+        _call('dbn_render_minmax', dev, *common, mm.data_ptr())
+    _call('dbn_render_paint', dev, src.data_ptr(), out.data_ptr(), *common, mm.data_ptr() if auto else None, lut.data_ptr(), a)
     return out
 
 
@@ -335,7 +328,7 @@ def glyph_table():
 def _font_on(dev):
     if dev not in _font_dev:
         f = glyph_table()
-        _font_dev[dev] = (_to_device(f['edges'], dev), _to_device(f['index'], dev))
+        _font_dev[dev] = (upload(f['edges'], dev), upload(f['index'], dev))
     return _font_dev[dev]
 
 
@@ -442,14 +435,9 @@ def _out_buffer(packed, shapes, out, device):
                 and out.numel() == packed.numel() and (device is None or out.device == torch.device(device))):
             raise ValueError('out must be a packed uint8 device tensor of %d bytes%s' % (packed.numel(), '' if device is None else ' on %s' % (device, )))
         return out, out, out.device
-    dev = _device(packed, device)
-    src = _packed(packed, shapes, dev)
+    dev = cuda_device('rendering', device, packed)
+    src = packed_on(packed, shapes, dev)
     return src, torch.empty_like(src), dev
-
-
-def _image_desc(shapes, dev):
-    desc = np.stack([_offsets([h * w * 3 for h, w in shapes])[:-1], [h for h, _ in shapes], [w for _, w in shapes]], 1).astype(np.int64)
-    return _to_device(desc, dev)
 
 
 def draw_labels(images, labels_per_image, color=(255, 0, 0), height=16, background=None, out=None, device=None):
@@ -469,7 +457,7 @@ def draw_labels(images, labels_per_image, color=(255, 0, 0), height=16, backgrou
     Returns the packed uint8 device copy with the labels; out: a packed uint8 device buffer that already holds the picture
     (e.g. the result of draw_outlines), painted in place and returned, `images` then only gives the shapes.  One launch
     (dbn_draw_glyphs), two with a background, on the current stream."""
-    packed, shapes = _images(images)
+    packed, shapes = as_images(images)
     c = _color(color)
     bg = _color(background) if background is not None else None
     s = _size64(height)
@@ -478,18 +466,17 @@ def draw_labels(images, labels_per_image, color=(255, 0, 0), height=16, backgrou
     src, out, dev = _out_buffer(packed, shapes, out, device)
     if src.numel() == 0:
         return out
-    d = _image_desc(shapes, dev)
+    d = image_table(shapes, dev)
     if bg is not None:
         e, g, r = label_backgrounds(labels_per_image, N, s)
-        te, tg, tr = (_to_device(a, dev) if len(a) else None for a in (e, g, r))
-        _call('dbn_draw_glyphs', src.data_ptr(), out.data_ptr(), src.numel(), d.data_ptr(), N, te.data_ptr() if len(r) else None, len(e),
-              tg.data_ptr() if len(r) else None, len(g), tr.data_ptr() if len(r) else None, len(r), s, _rows_bound(g, s), bg[0], bg[1], bg[2],
-              _stream(dev))
+        te, tg, tr = (upload(a, dev) if len(a) else None for a in (e, g, r))
+        _call('dbn_draw_glyphs', dev, src.data_ptr(), out.data_ptr(), src.numel(), d.data_ptr(), N, te.data_ptr() if len(r) else None, len(e),
+              tg.data_ptr() if len(r) else None, len(g), tr.data_ptr() if len(r) else None, len(r), s, _rows_bound(g, s), bg[0], bg[1], bg[2])
         src = out
     fe, fg = _font_on(dev)
-    tr = _to_device(recs, dev) if len(recs) else None
-    _call('dbn_draw_glyphs', src.data_ptr(), out.data_ptr(), src.numel(), d.data_ptr(), N, fe.data_ptr(), fe.shape[0], fg.data_ptr(), fg.shape[0],
-          tr.data_ptr() if tr is not None else None, len(recs), s, _rows_bound(glyph_table()['index'], s), c[0], c[1], c[2], _stream(dev))
+    tr = upload(recs, dev) if len(recs) else None
+    _call('dbn_draw_glyphs', dev, src.data_ptr(), out.data_ptr(), src.numel(), d.data_ptr(), N, fe.data_ptr(), fe.shape[0], fg.data_ptr(), fg.shape[0],
+          tr.data_ptr() if tr is not None else None, len(recs), s, _rows_bound(glyph_table()['index'], s), c[0], c[1], c[2])
     return out
 
 
@@ -498,7 +485,7 @@ def draw_dots(images, points_per_image, color=(0, 255, 0), out=None, device=None
     height H a disc of diameter d = int(H * 0.01) about every (x, y) of points_per_image[n], none where d is 0.  A disc is
     one zero-length edge through dbn_draw_strokes (d = 1: the pixel itself; d >= 2: 4 r^2 <= d^2, this project's stroke):
     one launch per distinct d > 0, in ascending order.  out: as draw_labels."""
-    packed, shapes = _images(images)
+    packed, shapes = as_images(images)
     c = _color(color)
     if not isinstance(points_per_image, (list, tuple)) or len(points_per_image) != len(shapes):
         raise ValueError('points for %s images, but %d images' % (len(points_per_image) if isinstance(points_per_image, (list, tuple)) else '?', len(shapes)))
@@ -513,13 +500,13 @@ def draw_dots(images, points_per_image, color=(0, 255, 0), out=None, device=None
     src, out, dev = _out_buffer(packed, shapes, out, device)
     if src.numel() == 0:
         return out
-    desc = _image_desc(shapes, dev)
+    desc = image_table(shapes, dev)
     if not by_d and src is not out:
         out.copy_(src)
     for d in sorted(by_d):
-        e = _to_device(np.array(by_d[d], np.int32), dev)
-        _call('dbn_draw_strokes', src.data_ptr(), out.data_ptr(), src.numel(), desc.data_ptr(), len(shapes), e.data_ptr(), len(by_d[d]), d, c[0], c[1],
-              c[2], _stream(dev))
+        e = upload(np.array(by_d[d], np.int32), dev)
+        _call('dbn_draw_strokes', dev, src.data_ptr(), out.data_ptr(), src.numel(), desc.data_ptr(), len(shapes), e.data_ptr(), len(by_d[d]), d, c[0],
+              c[1], c[2])
         src = out
     return out
 
@@ -548,7 +535,7 @@ def draw_words(images, words_per_image, color=(255, 0, 0), height=16, dots=True,
     there first.  The same bytes and launches as draw_dots(images, anchors, dot_color) followed by
     draw_labels(..., out=that result), which is how it runs (all dots, then all text: the reference goes word by word, so
     there a later dot may cover earlier text).  Label text is this project's definition (draw_labels), not cv2's."""
-    packed, shapes = _images(images)
+    packed, shapes = as_images(images)
     labels = _words_of(words_per_image, len(shapes))
     if dots:
         out = draw_dots((packed, shapes), [[p for _, p in labs] for labs in labels], dot_color, out=out, device=device)
@@ -580,7 +567,7 @@ def draw_scores(images, detections_per_image, fmt='%.2f', color=(255, 0, 0), hei
     """Every detection's score written at its first vertex, for the (boxes, scores) pairs of detect_boxes and the (polygons,
     scores) pairs of detect_polygons alike: draw_labels(images, score_labels(detections, N, fmt), ...).  Needs no
     recogniser.  Label text is this project's definition (draw_labels), not cv2's."""
-    packed, shapes = _images(images)
+    packed, shapes = as_images(images)
     return draw_labels((packed, shapes), score_labels(detections_per_image, len(shapes), fmt), color, height, background, out=out, device=device)
 
 
@@ -593,7 +580,7 @@ def render_detections(images, prob, shapes_per_image, valid_hw=None, color=(255,
     output of recognize_words) the recognised strings with their anchor dots (draw_words(images, words, out=...)), in
     that order, in `color` at cap height `height`, after the map so that they stay readable.  Label text is this
     project's definition (draw_labels), not cv2.putText's."""
-    packed, shapes = _images(images)
+    packed, shapes = as_images(images)
     out = draw_outlines((packed, shapes), shapes_per_image, color, thickness, device=prob.device if isinstance(prob, torch.Tensor) else None)
     if heatmap:
         out = overlay_heatmap((packed, shapes), prob, valid_hw, cmap, alpha, vmin, vmax, out=out)
@@ -617,7 +604,7 @@ def minmax_scale_u8(x):
         raise ValueError('minmax_scale_u8: empty input or more than 65535 images')
     out = torch.empty((N, H, W, 3), device=x.device, dtype=torch.uint8)
     mm = torch.empty(2 * N, device=x.device, dtype=torch.int32)
-    _call('dbn_minmax_scale_u8', x4.data_ptr(), N, H, W, mm.data_ptr(), out.data_ptr(), _stream(x.device))
+    _call('dbn_minmax_scale_u8', x.device, x4.data_ptr(), N, H, W, mm.data_ptr(), out.data_ptr())
     return out[0] if single else out
 
 

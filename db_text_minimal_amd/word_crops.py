@@ -29,7 +29,8 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
-from .augment import _MAX_SIDE, _check_shape, _offsets, _packed, _stream, _to_device
+from .packed import MAX_SIDE, as_images, cuda_device, image_table, on_device, packed_on, upload
+from .packed import offsets as _offsets
 
 SIZE = (32, 100)  # (h, w) of test_ocr.py / test_webcam.py / utils.py
 _WP_PX, _INT_MAX = 1024, 2 ** 31 - 1  # output pixels per workgroup of warp_perspective_u8
@@ -42,8 +43,8 @@ def _size(size):
         h, w = (int(v) for v in size)
     except (TypeError, ValueError):
         raise ValueError('size must be (height, width), got %r' % (size, ))
-    if not (1 <= h <= _MAX_SIDE and 1 <= w <= _MAX_SIDE):
-        raise ValueError('crop size %d x %d outside 1 .. %d' % (h, w, _MAX_SIDE))
+    if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+        raise ValueError('crop size %d x %d outside 1 .. %d' % (h, w, MAX_SIDE))
     return h, w
 
 
@@ -68,23 +69,6 @@ def perspective_maps(quads, size=SIZE):
     inv = np.zeros((K, 3, 3), np.float64)
     check(lib().dbn_perspective_maps(q.ctypes.data, K, h, w, fwd.ctypes.data, inv.ctypes.data), 'perspective_maps')
     return fwd, inv
-
-
-def _images(images):
-    """-> (packed uint8 tensor, [(H, W)]): image_collate's (packed, shapes, ...) or one uint8 [H, W, 3] tensor"""
-    if isinstance(images, torch.Tensor):
-        if images.dtype != torch.uint8 or images.dim() != 3 or images.shape[2] != 3:
-            raise ValueError('a single image must be a uint8 [H, W, 3] tensor')
-        return images.contiguous().reshape(-1), [_check_shape(images.shape)]
-    if not isinstance(images, (tuple, list)) or len(images) < 2 or not isinstance(images[0], torch.Tensor):
-        raise ValueError('images must be (packed uint8 tensor, shapes) as image_collate gives them, or a uint8 [H, W, 3] tensor')
-    packed, shapes = images[0], [_check_shape(s) for s in images[1]]
-    if packed.dtype != torch.uint8 or packed.dim() != 1:
-        raise ValueError('the packed images must be a flat uint8 tensor (image_collate)')
-    need = sum(h * w * 3 for h, w in shapes)
-    if packed.numel() != need:
-        raise ValueError('the packed images hold %d bytes, the shapes need %d' % (packed.numel(), need))
-    return packed, shapes
 
 
 def select_boxes(boxes, scores=None, min_score=None):
@@ -137,30 +121,23 @@ def crop_words(images, boxes, size=SIZE, scores=None, min_score=None, device=Non
     device: where to crop (default: the packed images' device, else the current one).  One launch on the current
     stream; the maps are one host call."""
     h, w = _size(size)
-    packed, shapes = _images(images)
+    packed, shapes = as_images(images)
     quads, index = select_boxes(boxes, scores, min_score)
     if index.size and int(index[:, 0].max()) >= len(shapes):
         raise ValueError('boxes for %d images, but %d images' % (int(index[:, 0].max()) + 1, len(shapes)))
-    if device is not None:
-        dev = torch.device(device)
-    else:
-        dev = packed.device if packed.is_cuda else torch.device('cuda', torch.cuda.current_device())
-    if dev.type != 'cuda':
-        raise ValueError('crop_words runs on a GPU device, not %s' % dev)
+    dev = cuda_device('crop_words', device, packed)
     K = quads.shape[0]
     if h * w + _WP_PX > _INT_MAX or -(-K * h * w // _WP_PX) > _INT_MAX // 256:  # dbn_warp_perspective_u8's grid
         raise ValueError('%d crops of %d x %d are too many for one call' % (K, h, w))
-    src = _packed(packed, shapes, dev)
+    src = packed_on(packed, shapes, dev)
     crops = torch.empty((K, h, w, 3), device=dev, dtype=torch.uint8)
     if K == 0:
         return crops, index
-    src_off = _offsets([sh * sw * 3 for sh, sw in shapes])
-    hw = np.array(shapes, np.int64)[index[:, 0]]
-    desc = np.stack([src_off[index[:, 0]], hw[:, 0], hw[:, 1]], 1)
     _, inv = perspective_maps(quads, (h, w))
-    d, m = _to_device(desc, dev), _to_device(inv, dev)
-    check(lib().dbn_warp_perspective_u8(src.data_ptr(), src.numel(), d.data_ptr(), m.data_ptr(), K, h, w, crops.data_ptr(), crops.numel(),
-                                        _stream(dev)), 'warp_perspective_u8')
+    with on_device(dev) as st:
+        d, m = image_table(shapes, dev, index[:, 0]), upload(inv, dev)
+        check(lib().dbn_warp_perspective_u8(src.data_ptr(), src.numel(), d.data_ptr(), m.data_ptr(), K, h, w, crops.data_ptr(), crops.numel(), st),
+              'warp_perspective_u8')
     return crops, index
 
 
@@ -239,9 +216,7 @@ def polygon_ribbons_device(polygons, segments=32, ends='auto', return_info=False
     if ends not in ('auto', 'half'):
         raise ValueError("ends must be 'auto' or 'half', got %r" % (ends, ))
     counts, xy = _checked_vertices(polygons, ends)
-    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-    if dev.type != 'cuda':
-        raise ValueError('polygon_ribbons_device runs on a GPU device, not %s' % dev)
+    dev = cuda_device('polygon_ribbons_device', device)
     K = len(counts)
     knots, valid = torch.empty((K, S + 1, 4), device=dev, dtype=torch.int32), torch.empty(K, device=dev, dtype=torch.uint8)
     found, info = torch.empty((K, 2), device=dev, dtype=torch.int32), torch.empty((K, 3), device=dev, dtype=torch.float64)
@@ -251,9 +226,10 @@ def polygon_ribbons_device(polygons, segments=32, ends='auto', return_info=False
         both = np.empty(K + 1 + 2 * total, np.float64)  # the K + 1 offsets (as int64) and the vertices behind them: one copy
         both[:K + 1].view(np.int64)[:] = offs
         both[K + 1:] = xy.reshape(-1)
-        d = _to_device(both, dev)
-        check(lib().dbn_polygon_ribbons_device(d.data_ptr() + 8 * (K + 1), d.data_ptr(), K, total, S, int(ends == 'half'), knots.data_ptr(),
-                                               valid.data_ptr(), found.data_ptr(), info.data_ptr(), _stream(dev)), 'polygon_ribbons_device')
+        with on_device(dev) as st:
+            d = upload(both, dev)
+            check(lib().dbn_polygon_ribbons_device(d.data_ptr() + 8 * (K + 1), d.data_ptr(), K, total, S, int(ends == 'half'), knots.data_ptr(),
+                                                   valid.data_ptr(), found.data_ptr(), info.data_ptr(), st), 'polygon_ribbons_device')
     if return_info:
         return knots, valid, dict(ends=found, E=info[:, 0].contiguous(), width=info[:, 1].contiguous(), length=info[:, 2].contiguous())
     return knots, valid
@@ -297,9 +273,9 @@ def rectify_from_ribbons(images, knots, valid, image_index, size=SIZE, device=No
     device that cuts the crops, as polygon_ribbons_device returns them), which are used in place.  -> uint8 [K, h, w, 3]
     on the device."""
     h, w = _size(size)
-    packed, shapes = _images(images)
-    on_device = isinstance(knots, torch.Tensor) or isinstance(valid, torch.Tensor)
-    if on_device:  # polygon_ribbons_device's tensors, used where they are
+    packed, shapes = as_images(images)
+    ribbons_there = isinstance(knots, torch.Tensor) or isinstance(valid, torch.Tensor)
+    if ribbons_there:  # polygon_ribbons_device's tensors, used where they are
         for name, a, dtype in (('knots', knots, torch.int32), ('valid', valid, torch.uint8)):
             if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == dtype and a.is_contiguous()):
                 raise ValueError('%s on the device must be a contiguous %s CUDA tensor (and so must the other)' % (name, dtype))
@@ -308,7 +284,7 @@ def rectify_from_ribbons(images, knots, valid, image_index, size=SIZE, device=No
     if knots.ndim != 3 or knots.shape[2] != 4:
         raise ValueError('knots must be int32 [K, S + 1, 4], got shape %s' % (tuple(knots.shape), ))
     K, S = knots.shape[0], _segments(knots.shape[1] - 1)
-    valid = valid.reshape(-1) if on_device else np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)
+    valid = valid.reshape(-1) if ribbons_there else np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)
     image_index = np.ascontiguousarray(image_index, dtype=np.int64).reshape(-1)
     if valid.shape[0] != K or image_index.shape[0] != K:
         raise ValueError('%d ribbons, %d valid flags, %d image indices' % (K, valid.shape[0], image_index.shape[0]))
@@ -317,22 +293,18 @@ def rectify_from_ribbons(images, knots, valid, image_index, size=SIZE, device=No
     # dbn_rectify_u8: h w <= 2^30 keeps the 64-bit pixel arithmetic exact for any int32 knots; the grid is one run of blocks
     if h * w > _RC_MAX_HW or K * -(-h * w // _RC_PX) > _INT_MAX:
         raise ValueError('%d crops of %d x %d are too many or too large for one call' % (K, h, w))
-    dev = torch.device(device) if device is not None else (packed.device if packed.is_cuda else torch.device('cuda', torch.cuda.current_device()))
-    if dev.type != 'cuda':
-        raise ValueError('rectify_words runs on a GPU device, not %s' % dev)
-    if on_device and {knots.device.index, valid.device.index} != {torch.cuda.current_device() if dev.index is None else dev.index}:
+    dev = cuda_device('rectify_words', device, packed)
+    if ribbons_there and {knots.device, valid.device} != {dev}:
         raise ValueError('knots on %s and valid on %s, the crops are cut on %s' % (knots.device, valid.device, dev))
-    src = _packed(packed, shapes, dev)
+    src = packed_on(packed, shapes, dev)
     crops = torch.empty((K, h, w, 3), device=dev, dtype=torch.uint8)
     if K == 0:
         return crops
-    src_off = _offsets([sh * sw * 3 for sh, sw in shapes])
-    hw = np.array(shapes, np.int64)[image_index]
-    desc = np.stack([src_off[image_index], hw[:, 0], hw[:, 1]], 1)
-    d = _to_device(desc, dev)
-    kn, va = (knots, valid) if on_device else (_to_device(knots, dev), _to_device(valid, dev))
-    check(lib().dbn_rectify_u8(src.data_ptr(), src.numel(), d.data_ptr(), kn.data_ptr(), va.data_ptr(), K, S, h, w, crops.data_ptr(),
-                               crops.numel(), _stream(dev)), 'rectify_u8')
+    with on_device(dev) as st:
+        d = image_table(shapes, dev, image_index)
+        kn, va = (knots, valid) if ribbons_there else (upload(knots, dev), upload(valid, dev))
+        check(lib().dbn_rectify_u8(src.data_ptr(), src.numel(), d.data_ptr(), kn.data_ptr(), va.data_ptr(), K, S, h, w, crops.data_ptr(),
+                                   crops.numel(), st), 'rectify_u8')
     return crops
 
 
@@ -352,7 +324,7 @@ def rectify_words(images, polygons, size=SIZE, scores=None, min_score=None, segm
     _size(size)
     if not (isinstance(ribbons, str) and ribbons in ('host', 'device')):
         raise ValueError("ribbons must be 'host' or 'device', got %r" % (ribbons, ))
-    packed, shapes = _images(images)
+    packed, shapes = as_images(images)
     kept, index = select_polygons(polygons, scores, min_score)
     if index.size and int(index[:, 0].max()) >= len(shapes):
         raise ValueError('polygons for %d images, but %d images' % (int(index[:, 0].max()) + 1, len(shapes)))

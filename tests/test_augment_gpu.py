@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from db_text_minimal_amd import augment as A
+from db_text_minimal_amd import packed as Pk
 from db_text_minimal_amd import (DBLoss, DBTextModel, DeviceBatches, FusedAdam, augment_images, image_collate, plan_augment,
                                  preprocess_image)
 from oracle import dbnet_oracle as O
@@ -63,7 +64,7 @@ def test_each_stage_bit_exact_on_mixed_batch():
     imgs = _images(rng, SHAPES)
     plans = _stage_plans()
     src = _packed(imgs)
-    off = A._offsets([h * w * 3 for h, w in SHAPES])
+    off = Pk.offsets([h * w * 3 for h, w in SHAPES])
     warped = A.warp_stage(src, off, SHAPES, plans, torch.device(DEV))
     cropped, coff, win_hw = A.cubic_stage(warped, off, SHAPES, plans, torch.device(DEV))
     out = A._letterbox_launch(cropped, coff, win_hw, plans, 640, 640, A.MEAN, torch.device(DEV))

@@ -154,6 +154,29 @@ def test_compiler_compares_the_header_with_the_definitions(tmp_path):
     assert res.returncode != 0 and "conflicting types for 'dbn_mfma_sustained_flops'" in res.stderr, res.stderr[-2000:]
 
 
+def test_no_module_imports_a_siblings_private_name():
+    """What the image-pipeline stages share is public in packed.py: no module of the package brings in an underscore-prefixed name
+    from a sibling other than _lib, and packed.py itself imports nothing from the package but _lib, so every stage can import it."""
+    import ast
+    pkg = os.path.join(ROOT, 'db_text_minimal_amd')
+    modules = sorted(f for f in os.listdir(pkg) if f.endswith('.py'))
+    assert 'packed.py' in modules and len(modules) >= 15
+    seen = 0
+    for f in modules:
+        for node in ast.walk(ast.parse(open(os.path.join(pkg, f)).read(), f)):
+            if isinstance(node, ast.ImportFrom) and node.level >= 1:
+                seen += 1
+                sibling = node.module or ''  # `from . import x`: the names are the siblings
+                private = [a.name for a in node.names if a.name.startswith('_') and not (sibling == '' and a.name == '_lib')]
+                assert sibling == '_lib' or not private, '%s: from .%s import %s' % (f, sibling, ', '.join(private))
+                if f == 'packed.py':
+                    assert sibling == '_lib' or [a.name for a in node.names] == ['_lib'], 'packed.py imports from .%s' % sibling
+            elif isinstance(node, (ast.Import, ast.ImportFrom)) and f == 'packed.py':
+                names = [node.module] if isinstance(node, ast.ImportFrom) else [a.name for a in node.names]
+                assert not any(n.split('.')[0] == 'db_text_minimal_amd' for n in names), names
+    assert seen >= 30  # (the walk still finds the relative imports)
+
+
 def test_size_queries_without_gpu():
     L = _lib.lib()
     assert L.dbn_igemm_packed_floats(7 * 7 * 4, 64) == 208 * 64  # K=196 padded to 208

@@ -10,6 +10,7 @@ import torch
 from db_text_minimal_amd import (detect_boxes, draw_dots, draw_labels, draw_outlines, draw_scores, draw_words, image_views, overlay_heatmap,
                                  render_detections, text_size)
 from db_text_minimal_amd import render as Rn
+from db_text_minimal_amd import packed as Pk
 from db_text_minimal_amd._lib import check, lib
 import labels_ref as LR
 import render_ref as R
@@ -147,7 +148,7 @@ def test_records_the_kernel_must_skip():
     imgs, buf, packed = _batch()
     before = buf.clone()
     N, n = len(SHAPES), packed.numel()
-    off = Rn._offsets([h * w * 3 for h, w in SHAPES])
+    off = Pk.offsets([h * w * 3 for h, w in SHAPES])
     desc = np.stack([off[:-1], [h for h, _ in SHAPES], [w for _, w in SHAPES]], 1).astype(np.int64)
     desc[0] = 0, 1, 65536             # a side past 65535
     desc[1] = -3, 5, 3                # starts before the buffer

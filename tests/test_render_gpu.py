@@ -9,6 +9,7 @@ import torch
 from db_text_minimal_amd import (detect_boxes, draw_outlines, image_collate, image_views, minmax_scale_u8, overlay_heatmap,
                                  render_detections)
 from db_text_minimal_amd import render as Rn
+from db_text_minimal_amd import packed as Pk
 from db_text_minimal_amd._lib import check, lib
 import render_ref as R
 from gpu_util import DEV
@@ -268,7 +269,7 @@ def test_every_output_byte_written_and_nothing_past_it(shapes, shift):
     buf.fill_(0xA5)
     boxes = [_shapes_for(rng, H, W, 9) for H, W in shapes]
     edges = torch.from_numpy(Rn.stroke_edges(boxes, N)).to(DEV)
-    off = Rn._offsets([h * w * 3 for h, w in shapes])
+    off = Pk.offsets([h * w * 3 for h, w in shapes])
     idesc = torch.from_numpy(np.stack([off[:-1], [h for h, _ in shapes], [w for _, w in shapes]], 1).astype(np.int64)).to(DEV)
     check(lib().dbn_draw_strokes(packed.data_ptr(), dst.data_ptr(), n, idesc.data_ptr(), N, edges.data_ptr(), len(edges), 3, 9, 8, 7, st), 'draw_strokes')
     torch.cuda.synchronize()

@@ -8,6 +8,7 @@ import torch
 
 from db_text_minimal_amd import crop_words, detect_boxes, image_collate, perspective_maps
 from db_text_minimal_amd import word_crops as Wc
+from db_text_minimal_amd import packed as Pk
 from db_text_minimal_amd._lib import check, lib
 import crop_ref as R
 from gpu_util import DEV
@@ -123,7 +124,7 @@ def test_more_than_65535_crops_in_one_call():
 
 def _launch(packed, shapes, quads, img_of, size, dst, src_off_override=None):
     """dbn_warp_perspective_u8 into a caller's buffer, with the descriptors crop_words builds"""
-    off = Wc._offsets([h * w * 3 for h, w in shapes])
+    off = Pk.offsets([h * w * 3 for h, w in shapes])
     hw = np.array(shapes, np.int64)[img_of]
     desc = np.stack([off[img_of], hw[:, 0], hw[:, 1]], 1)
     if src_off_override is not None:

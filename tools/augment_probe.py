@@ -24,6 +24,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 from db_text_minimal_amd import augment as A  # noqa: E402
+from db_text_minimal_amd import packed as Pk  # noqa: E402
 from db_text_minimal_amd._lib import check, lib  # noqa: E402
 import augment_ref as R  # noqa: E402
 
@@ -116,7 +117,7 @@ def main():
 
     packed_host = torch.from_numpy(np.concatenate([i.reshape(-1) for i in imgs])).pin_memory()
     src = packed_host.to(dev)
-    off = A._offsets([H * W * 3] * N)
+    off = Pk.offsets([H * W * 3] * N)
     L = lib()
     stream = torch.cuda.current_stream().cuda_stream
     dd = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731

@@ -28,6 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 from db_text_minimal_amd import crop_words, perspective_maps  # noqa: E402
 from db_text_minimal_amd import word_crops as Wc  # noqa: E402
+from db_text_minimal_amd import packed as Pk  # noqa: E402
 from db_text_minimal_amd._lib import check, lib  # noqa: E402
 import crop_ref as R  # noqa: E402
 
@@ -111,7 +112,7 @@ def main():
         t_maps.append(1e3 * (time.perf_counter() - t0))
     say('host   perspective_maps (measured, one core): %.3f ms for %d quads (median of %d)' % (statistics.median(t_maps), K, len(t_maps)))
 
-    off = Wc._offsets([H * W * 3] * N)
+    off = Pk.offsets([H * W * 3] * N)
     desc = np.stack([off[index[:, 0]], np.full(K, H, np.int64), np.full(K, W, np.int64)], 1)
     d, m = torch.from_numpy(desc).to(dev), torch.from_numpy(inv).to(dev)
     crops = torch.empty((K, h, w, 3), device=dev, dtype=torch.uint8)

@@ -26,6 +26,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from db_text_minimal_amd import jpeg as J  # noqa: E402
+from db_text_minimal_amd import packed as Pk  # noqa: E402
 
 
 def images(kind):
@@ -77,7 +78,7 @@ def probe(kind, reps, pillow):
     items = [(i * h * w * 3, h, w, 3) for i in range(n)]
     tables = J.quant_tables(75)
     hdesc, qtabs, total, tp, tf = J.forward_plan(items, '420', tables)
-    desc, qt, a, b = (J._up(v, dev) for v in (hdesc, qtabs.view(np.int16), tp, tf))
+    desc, qt, a, b = (Pk.upload(v, dev) for v in (hdesc, qtabs.view(np.int16), tp, tf))
     coef = torch.empty(total, dtype=torch.int16, device=dev)
     planes = torch.empty(total, dtype=torch.uint8, device=dev)
     host = torch.empty(total, dtype=torch.int16, pin_memory=True)

@@ -88,6 +88,7 @@ def main():
 
     import torch
     from db_text_minimal_amd import draw_labels, image_views
+    from db_text_minimal_amd import packed as Pk
     from db_text_minimal_amd import render as Rn
     from db_text_minimal_amd._lib import check, lib
     import labels_ref as LR
@@ -103,7 +104,7 @@ def main():
         f = Rn.glyph_table()
         ext = (f['index'][recs[:, 1], 4:6].astype(np.int64) - f['index'][recs[:, 1], 2:4]) * s / (64 * 2048)
         fe, fg = Rn._font_on(dev)
-        r, d, out = torch.from_numpy(recs).to(dev), Rn._image_desc(shapes, dev), src.clone()
+        r, d, out = torch.from_numpy(recs).to(dev), Pk.image_table(shapes, dev), src.clone()
         rows = Rn._rows_bound(f['index'], s)
 
         def kernel():

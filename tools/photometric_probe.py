@@ -78,6 +78,7 @@ def main():
     import torch
     sys.path.insert(0, ROOT)
     from db_text_minimal_amd import color_jitter_images, plan_color_jitter
+    from db_text_minimal_amd import packed as Pk
     from db_text_minimal_amd import photometric as P
     from db_text_minimal_amd._lib import lib
     dev = torch.device('cuda')
@@ -131,7 +132,7 @@ def main():
         plans = plan_color_jitter(n, np.random.RandomState(1), **kw)
         moved = nbytes * (3 if 'contrast' in kw else 2)
         hdesc = P.plan_records(shapes, plans)
-        desc = P._up(hdesc, dev)
+        desc = Pk.upload(hdesc, dev)
 
         def launches():
             P.check(L.dbn_color_jitter_u8(packed.data_ptr(), out.data_ptr(), nbytes, hdesc.ctypes.data, desc.data_ptr(), n, sums.data_ptr(), stream),

@@ -78,6 +78,7 @@ def main():
     args = ap.parse_args()
     import torch
     sys.path.insert(0, ROOT)
+    from db_text_minimal_amd import packed as Pk
     from db_text_minimal_amd import png as P
     from db_text_minimal_amd._lib import lib
     dev = torch.device('cuda')
@@ -126,7 +127,7 @@ def main():
     # the two launches, on tensors already on the device
     hdesc, hsubs = np.ascontiguousarray(obj.desc), np.ascontiguousarray(obj.subs)
     out_bytes = n * h * w * 3
-    blob, desc, subs, pal = obj.blob.to(dev), P._up(hdesc, dev), P._up(hsubs, dev), P._up(obj.palettes, dev)
+    blob, desc, subs, pal = obj.blob.to(dev), Pk.upload(hdesc, dev), Pk.upload(hsubs, dev), Pk.upload(obj.palettes, dev)
     raw = torch.empty(obj.raw_bytes, dtype=torch.uint8, device=dev)
     out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
     L, stream = lib(), torch.cuda.current_stream().cuda_stream

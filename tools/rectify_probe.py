@@ -34,6 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 from db_text_minimal_amd import perspective_maps, polygon_ribbons, polygon_ribbons_device, rectify_words  # noqa: E402
 from db_text_minimal_amd import word_crops as Wc  # noqa: E402
+from db_text_minimal_amd import packed as Pk  # noqa: E402
 from db_text_minimal_amd._lib import check, lib  # noqa: E402
 import rectify_ref as R  # noqa: E402
 from crop_probe import time_launch, time_wall  # noqa: E402
@@ -73,7 +74,7 @@ def time_device_ribbons(L, polys, S, half, dev, stream, reps):
     """dbn_polygon_ribbons_device alone on polygons already on the device -> (median ms, its outputs on the host)"""
     K = len(polys)
     xy = torch.from_numpy(np.concatenate(polys).astype(np.float64)).to(dev)
-    offs = torch.from_numpy(Wc._offsets([len(p) for p in polys])).to(dev)
+    offs = torch.from_numpy(Pk.offsets([len(p) for p in polys])).to(dev)
     knots, valid = torch.empty((K, S + 1, 4), device=dev, dtype=torch.int32), torch.empty(K, device=dev, dtype=torch.uint8)
     found, info = torch.empty((K, 2), device=dev, dtype=torch.int32), torch.empty((K, 3), device=dev, dtype=torch.float64)
 
@@ -141,7 +142,7 @@ def main():
     say("largest one polygon of 256 vertices, 64 segments, ends='auto' (measured): device launch %.3f ms, host call %.1f ms (one thread, with "
         "its early exit); %s" % (t, 1e3 * (time.perf_counter() - t0), 'EQUAL' if same else 'DIFFERENT'))
 
-    off = Wc._offsets([H * W * 3] * N)
+    off = Pk.offsets([H * W * 3] * N)
     desc = np.stack([off[index[:, 0]], np.full(K, H, np.int64), np.full(K, W, np.int64)], 1)
     d, kn, va = torch.from_numpy(desc).to(dev), torch.from_numpy(knots).to(dev), torch.from_numpy(valid).to(dev)
     crops = torch.empty((K, h, w, 3), device=dev, dtype=torch.uint8)

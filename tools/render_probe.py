@@ -30,6 +30,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 from db_text_minimal_amd import image_views, render_detections  # noqa: E402
 from db_text_minimal_amd import render as Rn  # noqa: E402
+from db_text_minimal_amd import packed as Pk  # noqa: E402
 from db_text_minimal_amd._lib import check, lib  # noqa: E402
 import render_ref as R  # noqa: E402
 
@@ -91,7 +92,7 @@ def workload(say, rng, N, H, W, reps):
     say('render_probe: %d x %dx%d uint8, %d boxes per image at thickness %d, maps %d x %d' % (N, H, W, PER_IMAGE, THICKNESS, MAP, MAP))
     L, st = lib(), torch.cuda.current_stream().cuda_stream
     edges = Rn.stroke_edges(boxes, N)
-    off = Rn._offsets([H * W * 3] * N)
+    off = Pk.offsets([H * W * 3] * N)
     idesc = torch.from_numpy(np.stack([off[:-1], np.full(N, H), np.full(N, W)], 1).astype(np.int64)).to(dev)
     e = torch.from_numpy(edges).to(dev)
     out = torch.empty_like(src)
