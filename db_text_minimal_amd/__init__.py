@@ -2,7 +2,8 @@
 DBLoss, per-step update) behind the call surface of huyhoang17/DB_text_minimal."""
 from .losses import DBLoss  # noqa: F401
 from .models import DBTextModel  # noqa: F401
-from .optim import FusedAdam  # noqa: F401
+from .optim import FusedAdam, FusedAdamW, FusedSGD, split_decay  # noqa: F401
+from .lr_schedulers import WarmupPolyLR  # noqa: F401
 from .train import DBTrainer  # noqa: F401
 from .gt_maps import gt_collate, make_gt_maps, normalize_images, offset_polygon  # noqa: F401
 from .postprocess import SegDetectorRepresenter, detect_boxes, detect_polygons  # noqa: F401

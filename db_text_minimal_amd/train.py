@@ -17,6 +17,7 @@ Gradient accumulation (`FusedAdam(accumulation_steps=k)`, optim.py): every call 
 backward on its micro-batch and folds the flat gradient into the optimizer's accumulator; the k-th call of a cycle then
 exchanges the ACCUMULATOR (one all-reduce per cycle: k times fewer collectives) and updates with grad_scale = 1 / (world k).
 """
+import contextlib
 import os
 
 import torch
@@ -25,7 +26,7 @@ import torch.distributed as dist
 from . import _lib
 from . import engine as engine_mod
 from ._lib import check
-from .optim import FusedAdam
+from .optim import FlatOptimizer, FusedAdam
 
 GT_KEYS = ('prob_map', 'supervision_mask', 'thresh_map', 'text_area_map')  # train.py:163-166 order
 
@@ -203,15 +204,13 @@ class DBTrainer:
         for b in self.model.buffers():
             dist.broadcast(b, src=src, group=self.pg)
         opt = self.optimizer
-        if isinstance(opt, FusedAdam):
+        if isinstance(opt, FlatOptimizer):
             opt._ensure_state()
             cnt = torch.tensor([opt.step_count], device=eng.flat.device, dtype=torch.int64)
             dist.broadcast(cnt, src=src, group=self.pg)
             opt.step_count = int(cnt.item())
-            dist.broadcast(opt.exp_avg, src=src, group=self.pg)
-            dist.broadcast(opt.exp_avg_sq, src=src, group=self.pg)
-            if opt.max_exp_avg_sq is not None:
-                dist.broadcast(opt.max_exp_avg_sq, src=src, group=self.pg)
+            for t in opt.state_tensors():  # (FusedAdam: exp_avg, exp_avg_sq and, with amsgrad, max_exp_avg_sq)
+                dist.broadcast(t, src=src, group=self.pg)
         eng.mark_params_dirty()
         self._need_sync = False
 
@@ -225,7 +224,7 @@ class DBTrainer:
         preds = eng.forward(img, train=True)
         _, dpreds = self._loss(preds, gts)
         eng.backward(dpreds)
-        if isinstance(self.optimizer, FusedAdam):
+        if isinstance(self.optimizer, FlatOptimizer):
             self.optimizer._ensure_state()
         eng.nbt_pending = {}
         with torch.no_grad():
@@ -559,7 +558,7 @@ def evaluate(model, criterion, loader, thresh=0.3, device=None, pixel_metric=Tru
 
 def fit(model, criterion, optimizer, train_loader, test_loader=None, epochs=1, scheduler=None, lrs_mode=None, thresh=0.3,
         best_cp_path=None, last_cp_path=None, device=None, log=None, process_group=None, trainer=None, pixel_metric=True,
-        detection=None, best_hmean_cp_path=None):
+        detection=None, best_hmean_cp_path=None, ema_eval=False):
     """The reference's training driver (train.py:146-318): per epoch a pass over `train_loader` through DBTrainer.step
     (lr scheduler stepped per iteration when lrs_mode == 'poly', train.py:172-173 — per UPDATE under gradient accumulation:
     on the last call of each cycle of optimizer.accumulation_steps; `global_steps` counts every call), the running pixel metric
@@ -577,7 +576,11 @@ def fit(model, criterion, optimizer, train_loader, test_loader=None, epochs=1, s
     detection (None: off, and every record, return value and timing is as without it): True or a dict over
     DETECTION_DEFAULTS — evaluate() also scores the test set's detections (train.py:276-299): each epoch record gains
     test_precision / test_recall / test_hmean, and `hmean >= best_hmean` (from 0) saves `best_hmean_cp_path`.  The counts
-    behind them are summed over the ranks, so the save decision is rank-uniform."""
+    behind them are summed over the ranks, so the save decision is rank-uniform.
+
+    ema_eval (default False: nothing changes): when true and the optimizer keeps an exponential moving average of the weights
+    (FusedSGD / FusedAdamW with ema_decay), evaluate() runs inside optimizer.ema_weights() and every checkpoint written here holds
+    optimizer.ema_state_dict(): the averaged parameters with the model's BatchNorm buffers.  Training goes on with the model's own."""
     own_trainer = trainer is None
     if own_trainer:
         # (the heap freeze of DBTrainer.freeze_heap is taken for the duration of this call and undone on return)
@@ -585,6 +588,7 @@ def fit(model, criterion, optimizer, train_loader, test_loader=None, epochs=1, s
                             gc_freeze=os.environ.get('DBN_GC_FREEZE', '1') == '1')
     distributed = dist.is_available() and dist.is_initialized()
     is_writer = (not distributed) or dist.get_rank(process_group) == 0
+    use_ema = bool(ema_eval) and getattr(optimizer, 'ema_decay', None) is not None
     ctl_dev = _collective_device(model) if distributed else None
     RunningScore = None
     if pixel_metric:
@@ -595,7 +599,7 @@ def fit(model, criterion, optimizer, train_loader, test_loader=None, epochs=1, s
         file is complete when any rank returns.  The BatchNorm buffers in it are rank 0's.  Called at rank-uniform points
         only (the decision values are all-reduced first)."""
         if is_writer:
-            torch.save(model.state_dict(), path)
+            torch.save(optimizer.ema_state_dict() if use_ema else model.state_dict(), path)
         if distributed:
             dist.barrier(group=process_group)
 
@@ -621,11 +625,12 @@ def fit(model, criterion, optimizer, train_loader, test_loader=None, epochs=1, s
         train_loss = float(train_sum) if train_sum is not None else float('nan')
         test_loss, test_score = float('nan'), {}
         if test_loader is not None:
-            if detection is None:
-                test_loss, test_score = evaluate(model, criterion, test_loader, thresh=thresh, device=device, pixel_metric=pixel_metric)
-            else:
-                test_loss, test_score = evaluate(model, criterion, test_loader, thresh=thresh, device=device, pixel_metric=pixel_metric,
-                                                 detection=detection, process_group=process_group)
+            with (optimizer.ema_weights() if use_ema else contextlib.nullcontext()):
+                if detection is None:
+                    test_loss, test_score = evaluate(model, criterion, test_loader, thresh=thresh, device=device, pixel_metric=pixel_metric)
+                else:
+                    test_loss, test_score = evaluate(model, criterion, test_loader, thresh=thresh, device=device,
+                                                     pixel_metric=pixel_metric, detection=detection, process_group=process_group)
         local = (train_loss, test_loss)
         train_loss, test_loss = _mean_over_ranks(local, process_group, ctl_dev)  # rank-uniform from here on
         rec = {'epoch': epoch + 1, 'global_steps': steps, 'lr': optimizer.param_groups[0]['lr'], 'train_loss_sum': train_loss,

@@ -385,6 +385,33 @@ int dbn_grad_sqnorm(const float* g, long n, double* partials, double* out, void*
 int dbn_adam_step_ex(float* p, const float* g, float* m, float* v, float* vmax, long n, float lr, float beta1, float beta2, float eps,
                      float weight_decay, int step, float grad_scale, const double* sqnorm, float max_norm, void* stream);
 
+/* ---- optimizer family (csrc/optim_groups.hip): SGD with momentum and AdamW over one flat buffer, with per-group
+ *      learning rate and weight decay, the clip coefficient of dbn_adam_step_ex (same formula, same device value) and an optional
+ *      exponential moving average of the weights.
+ * Groups: `lr` and `weight_decay` are HOST arrays of `ngroups` floats (1 .. dbn_optim_max_groups() = 8), copied into the kernel arguments:
+ *      nothing is uploaded when a schedule changes them.  `run_end` / `run_group` are DEVICE arrays of `nruns` int32: run r covers the
+ *      quads (4 consecutive floats of the flat buffer) [run_end[r - 1], run_end[r]) and belongs to group run_group[r]; run_end ascends
+ *      and its last entry covers n / 4.  Elements past the last whole quad take the last run's group.  nruns = 0 (tables may be NULL)
+ *      means one group: that launch has no table, no LDS and no search.  nruns > dbn_optim_max_runs() = 1024 returns DBN_ERR_ARG.
+ * EMA: with shadow != NULL the thread that formed p' also writes shadow' = ema_decay shadow + ema_one_minus p' (the caller rounds d and
+ *      1 - d to fp32 once each); NULL moves no extra bytes.
+ * dbn_sgd_step, as torch.optim.SGD with clip_grad_norm_ in front (G: the element's group, s = grad_scale, coef as in dbn_adam_step_ex):
+ *      g = (coef s) acc + weight_decay[G] p;   buf' = g when `first`, else momentum buf + (1 - dampening) g
+ *      d = g + momentum buf' (nesterov) | buf' (momentum != 0) | g (momentum == 0: `buf` may be NULL and is not touched)
+ *      p' = p - lr[G] d
+ * dbn_adamw_step: the update of dbn_adam_step_ex (vmax != NULL: AMSGrad) with lr[G] / bc1.  decoupled = 0: g + weight_decay[G] p after the
+ *      clip (torch.optim.Adam(weight_decay); one group, shadow NULL: the bits of dbn_adam_step_ex).  decoupled = 1 (torch.optim.AdamW):
+ *      p <- p fp32(1 - lr[G] weight_decay[G]) first, then the update with the undecayed gradient. */
+int dbn_optim_max_groups(void);
+int dbn_optim_max_runs(void);
+int dbn_sgd_step(float* p, const float* g, float* buf, long n, const float* lr, const float* weight_decay, int ngroups, const int* run_end,
+                 const int* run_group, int nruns, float momentum, float dampening, int nesterov, int first, float grad_scale,
+                 const double* sqnorm, float max_norm, float* shadow, float ema_decay, float ema_one_minus, void* stream);
+int dbn_adamw_step(float* p, const float* g, float* m, float* v, float* vmax, long n, const float* lr, const float* weight_decay, int ngroups,
+                   const int* run_end, const int* run_group, int nruns, float beta1, float beta2, float eps, int decoupled, int step,
+                   float grad_scale, const double* sqnorm, float max_norm, float* shadow, float ema_decay, float ema_one_minus,
+                   void* stream);
+
 /* 1 when the library was built with -DDBN_EXPERIMENTS (make -C csrc EXP=1): adds the variants that were measured and rejected —
  * pre-split bf16 planes (at = 3, dbn_split3), the LDS-DMA fp32 weight gradient (dbn_set_wgrad_variant(1)), DBN_* environment
  * overrides of the tile / split heuristics.  The product library (default) has none of them: no getenv anywhere. */
