@@ -10,7 +10,8 @@ data_loaders.py:161-167, so a DataLoader ships decoded uint8 images of any size 
   augment_images(packed, shapes, plans)      device: fp32 [N, 3, S, S], normalised; plans=None is the letterbox
   preprocess_image(u8, size, pad)            device: utils.test_preprocess of one image
   DeviceBatches(loader, device, training)    raw batches -> the dicts fit / evaluate consume (img + GT maps); with
-                                             color_jitter the photometric stage (photometric.py) runs in front
+                                             color_jitter the photometric stage (photometric.py) runs in front,
+                                             with degrade the blur and noise stage (degrade.py) behind it
 
 Device stages (csrc/resample.hip), one launch each per batch on the current stream, no host sync: warp (flip + rotate,
 cv2.warpAffine INTER_LINEAR) -> cubic resize of the crop window only (cv2.resize INTER_CUBIC) -> linear letterbox resize
@@ -32,6 +33,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
+from .degrade import degrade_images, degrade_ranges, plan_degrade
 from .gt_maps import GT_KEYS, MEAN, make_gt_maps, plan_polygons
 from .jpeg import JpegCoefficients, JpegStreams, decode_coefficients, entropy_decode_device, stream_orientations
 from .packed import MAX_SIDE, check_shape, cuda_device, image_offsets, on_device, packed_on, pin_default, polys_tags, upload
@@ -365,11 +367,16 @@ class DeviceBatches:
     training=True the decoded uint8 batch then goes through color_jitter_images in front of the geometric steps, where
     MMOCR's DBNet pipeline has its ColorJitter.  Its plans are drawn from a second RandomState (seeded with
     [seed, JITTER_STREAM]), so the geometric plans of a seed are the same with and without it; None (the default), or
-    arguments that leave no operation present, make no draw and no launch."""
+    arguments that leave no operation present, make no draw and no launch.  degrade: a dict of plan_degrade's keyword
+    arguments (blur, blur_p, noise, noise_p, per_channel), e.g. {'blur': 3.0, 'noise': 10.0}; with training=True the batch
+    goes through degrade_images (degrade.py) behind the colour step and in front of the geometric ones, its plans drawn
+    from a third RandomState (seeded with [seed, DEGRADE_STREAM]); None, or arguments that leave neither operation
+    present, make no draw and no launch."""
 
     JITTER_STREAM = 0x636A  # second word of the colour stream's seed
+    DEGRADE_STREAM = 0x6467  # ... of the degradation stream's
 
-    def __init__(self, loader, device, training, size=640, seed=None, mean=MEAN, orient=False, color_jitter=None, **gt_kwargs):
+    def __init__(self, loader, device, training, size=640, seed=None, mean=MEAN, orient=False, color_jitter=None, degrade=None, **gt_kwargs):
         self.loader, self.device, self.training, self.size, self.mean = loader, torch.device(device), bool(training), int(size), mean
         self.orient = bool(orient)
         self.rng = np.random.RandomState(seed)
@@ -379,6 +386,11 @@ class DeviceBatches:
             self.color_jitter = dict(color_jitter)
             words = None if seed is None else np.append(np.asarray(seed, np.uint32).reshape(-1), np.uint32(self.JITTER_STREAM))
             self.jitter_rng = np.random.RandomState(words)
+        self.degrade = self.degrade_rng = None
+        if degrade is not None and degrade_ranges(**degrade):
+            self.degrade = dict(degrade)
+            words = None if seed is None else np.append(np.asarray(seed, np.uint32).reshape(-1), np.uint32(self.DEGRADE_STREAM))
+            self.degrade_rng = np.random.RandomState(words)
         self.gt_kwargs = gt_kwargs
 
     def __len__(self):
@@ -396,11 +408,13 @@ class DeviceBatches:
         if isinstance(packed, PngScanlines):  # png_collate: the device half of the decode
             packed, shapes = unfilter_png(packed, self.device)
         if self.training:
+            if (self.color_jitter is not None or self.degrade is not None) and not (isinstance(packed, torch.Tensor) and packed.is_cuda):
+                packed = packed_on(packed, shapes, self.device)  # image_collate's pinned host batch
             if self.color_jitter is not None:
-                if not (isinstance(packed, torch.Tensor) and packed.is_cuda):  # image_collate's pinned host batch
-                    packed = packed_on(packed, shapes, self.device)
                 colour_plans = plan_color_jitter(len(shapes), self.jitter_rng, **self.color_jitter)
                 packed = color_jitter_images(packed, shapes, colour_plans)
+            if self.degrade is not None:
+                packed = degrade_images(packed, shapes, plan_degrade(len(shapes), self.degrade_rng, **self.degrade))
             plans = plan_augment(shapes, polys, self.rng, self.size)
         else:
             plans = plan_letterbox(shapes, polys, self.size)

@@ -2,7 +2,7 @@
 
 A packed batch is (packed, shapes): a flat uint8 tensor that holds N images [H, W, 3] end to end, on the host or the device, and
 their [(H, W)]; image n starts at byte image_offsets(shapes)[n].  An image that was not decoded has shape (0, 0) and takes no bytes.
-The decoders write it; image_collate, color_jitter_images, augment_images, crop_words, the draw_* functions and the encoders take it.
+The decoders write it; image_collate, color_jitter_images, degrade_images, augment_images, crop_words, the draw_* functions and the encoders take it.
 
   check_shape, offsets, image_offsets, check_bytes, as_images, packed_on, flat_u8, image_table   the layout and its checks
   cuda_device, upload, stream, on_device                                                          where and how a stage launches

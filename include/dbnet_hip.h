@@ -1104,6 +1104,20 @@ int dbn_color_jitter_u8(const unsigned char* in, unsigned char* out, long bytes,
                         unsigned long long* sums, void* stream);
 int dbn_color_jitter_host(const unsigned char* in, unsigned char* out, long bytes, const long long* hdesc, int N);
 
+/* ---- Degradation augmentation (csrc/degrade.hip; db_text_minimal_amd/degrade.py): a Gaussian blur with a per-image radius, then additive
+ * Gaussian noise on the blurred byte, in exact integers, on packed uint8 [H][W][3] RGB images (the definition: DESIGN.md section 40).
+ * desc int64 [N][25] per image = {byte offset of its first pixel (any alignment; ascending, images do not overlap), H, W, first tile over the
+ * batch, r (0 .. 32; 0: no blur), S8 | per_channel << 32 (S8 = round(256 scale), 0 .. 16384; 0: no noise), the 64-bit seed, 0, then q_0 ..
+ * q_32 as 32-bit values, two to a field, the lower index in the low half}.  With r > 0 the weights q_0 .. q_r are below 65536, q_0 + 2 (q_1 +
+ * ... + q_r) = 65536, and those behind q_r are 0.  tiles int32 [T][3] = {image, y0, x0}: 32 rows x 64 columns from (y0, x0) of an image with
+ * r > 0 (cut at the image's edges), or {image, first pixel, 0}: a run of 3072 pixels in row-major order of an image with r = 0; per image in
+ * row-major order, images in order, every pixel in exactly one tile (the entry point refuses any other list).  normal int16 [4096]:
+ * round(4096 Phi^-1((k + 0.5) / 4096)).  1 <= N <= 65535, 1 <= H, W <= 16384.  Records and tiles are taken twice: in host memory (hdesc,
+ * htiles), checked against `bytes` before anything is launched, and in device memory (desc, tiles), which the kernel reads.  One launch, LDS
+ * sized by the largest r of the batch.  `out` must not overlap `in`; bytes of `out` that belong to no image are not written. */
+int dbn_degrade_u8(const unsigned char* in, unsigned char* out, long bytes, const long long* hdesc, const long long* desc, int N, const int* htiles,
+                   const int* tiles, long T, const short* normal, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
