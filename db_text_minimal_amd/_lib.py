@@ -115,6 +115,11 @@ class WinogradPackJob(ctypes.Structure):
     _fields_ = _fields('dbn_winograd_pack_job')
 
 
+class WinogradPlan(ctypes.Structure):
+    """dbn_winograd_plan of include/dbnet_hip.h: what dbn_winograd_describe reports (forms, rows, groups, splits; nothing is launched)."""
+    _fields_ = _fields('dbn_winograd_plan')
+
+
 class BnbFinal(ctypes.Structure):
     """dbn_bnb_final of include/dbnet_hip.h: the in-kernel finalize of a data gradient's BatchNorm-backward sums."""
     _fields_ = _fields('dbn_bnb_final')

@@ -484,6 +484,8 @@ int wwg_groups(int N, int H, int W) {
     if (wwg_linear(H, W)) return N * (int)(((long)((H + 1) / 2) * ((W + 1) / 2) + 31) / 32);
     return N * ((H + 7) / 8) * ((W + 15) / 16);
 }
+// 256 splits (the 64 -> 64 layers: one 64 x 64 block, every CU a split): the wide reduction (28 -> 20 us alone); fewer: round 4's
+bool wwg_wide(int nsplit) { return nsplit >= 128; }
 
 }  // namespace
 
@@ -537,13 +539,26 @@ int dbn_winograd_wgrad_f32(int phases, const float* dy, const float* x, const fl
     }
     if (phases & 2) {
         const int nsub = p.nob * p.nib;
-        // 256 splits (the 64 -> 64 layers: one 64 x 64 block, every CU a split): the wide form (28 -> 20 us alone); fewer: round 4's
-        if (p.nsplit >= 128)
+        if (wwg_wide(p.nsplit))
             hipLaunchKernelGGL(winograd_wgrad_reduce_kernel<32>, dim3(O, 2 * p.nib), dim3(256), 0, st, slab, p.nsplit, nsub, p.nib, I, grad, scale);
         else
             hipLaunchKernelGGL(winograd_wgrad_reduce_serial_kernel, dim3(O, p.nib), dim3(1024), 0, st, slab, p.nsplit, nsub, p.nib, I, grad, scale);
     }
     return dbn_status();
+}
+
+// The plans of winograd_f32_kernel and of the two kernels above for one map, described instead of launched (no device call)
+int dbn_winograd_describe(int N, int H, int W, int O, int Cb, void* plan) {
+    DBN_REQUIRE(plan && N > 0 && H > 0 && W > 0 && O > 0 && O % 64 == 0 && Cb > 0 && Cb % 64 == 0);
+    dbn_winograd_plan* const q = reinterpret_cast<dbn_winograd_plan*>(plan);
+    q->fwd_lin = dbn_winograd_linear(H, W);
+    q->fwd_rows = dbn_winograd_rows(N, H, W);
+    q->wgrad_lin = wwg_linear(H, W);
+    q->wgrad_groups = wwg_groups(N, H, W);
+    q->wgrad_nsub = (O / 64) * (Cb / 64);
+    q->wgrad_nsplit = wwg_splits(q->wgrad_groups, q->wgrad_nsub);
+    q->wgrad_wide = wwg_wide(q->wgrad_nsplit);
+    return DBN_OK;
 }
 
 }  // extern "C"

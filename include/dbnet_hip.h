@@ -324,6 +324,19 @@ int dbn_winograd_wgrad_linear(int H, int W); /* 1: small map, consecutive-tile f
 long dbn_winograd_wgrad_slab_floats(int N, int H, int W, int O, int Cb);
 int dbn_winograd_wgrad_f32(int phases, const float* dy, const float* x, const float* x_scale, const float* x_shift, float* slab, float* grad,
                            int N, int H, int W, int O, int Cb, int I, float scale, void* stream);
+/* What the Winograd kernels do on an N x H x W map with O output-gradient channels and Cb stored input channels, DESCRIBED
+ * instead of launched (host only: no device call): fills `plan` (host memory, dbn_winograd_plan) with the plans that
+ * dbn_winograd_conv_bn[_act]_f32 / dbn_winograd_dgrad_bnsums_f32 (fwd_*) and dbn_winograd_wgrad_f32 (wgrad_*) take — for the tests
+ * that prove which form a shape reaches.  fwd_lin / wgrad_lin: 1 = the consecutive-tile form, 0 = 8 x 16 pixel patches; fwd_rows =
+ * dbn_winograd_rows; wgrad_groups: patches or 32-tile groups of the whole batch, shared among wgrad_nsplit workgroups per
+ * wgrad_nsub = (O / 64) (Cb / 64) channel blocks (workgroup `split` takes groups split * groups / nsplit up to the next split's
+ * first); wgrad_wide: 1 = the slab reduction is winograd_wgrad_reduce_kernel<32>, 0 = the serial one.  Eligibility is not checked
+ * here (dbn_winograd_eligible, dbn_winograd_wgrad_eligible). */
+typedef struct dbn_winograd_plan {
+    int fwd_lin, fwd_rows;
+    int wgrad_lin, wgrad_groups, wgrad_nsub, wgrad_nsplit, wgrad_wide;
+} dbn_winograd_plan;
+int dbn_winograd_describe(int N, int H, int W, int O, int Cb, void* plan);
 
 /* ---- DBLoss (losses.py:18-40,48-66,75-82,105-139); preds [N,3|2,H,W], gts [4,N,H,W].
  * One launch: the workgroup that finishes last folds every workgroup's partial sums (fixed order) and writes losses[5] and

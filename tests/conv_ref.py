@@ -327,8 +327,12 @@ KSPLITS = (2, 5, 7)
 CONVT2 = (2, 64, 64, 8, 6)  # N, Ci, Co, H, W: ConvTranspose2d(k = 2, stride 2)
 CONVT_GENERAL = [(4, 6, 1), (8, 2, 0)]  # (stride, k, pad) on CONVT_GENERAL_SHAPE
 CONVT_GENERAL_SHAPE = (2, 64, 128, 5, 7)
-WINOGRAD_CASES = [(2, 64, 64, 13, 30), (2, 64, 64, 20, 20)]  # N, Ci, Co, H, W
-WINOGRAD_SEAM_CASES = [(3, 64, 64, 20, 20), (1, 64, 64, 10, 9), (2, 64, 64, 13, 30)]  # consecutive-tile form (two), ragged 8 x 16 patches
+# N, Ci, Co, H, W.  The forward / data-gradient kernel runs every one of these maps in its consecutive-tile (LIN) form (all are below 74
+# pixels wide); the weight gradient, whose rule differs, runs 13 x 30 in ragged 8 x 16 patches and the others in its LIN form — always with
+# as many workgroups as groups (one patch or 32-tile group each) and the serial slab reduction.  The patch form of the forward kernel,
+# several groups per workgroup and the wide reduction: WINO_FWD_PLAN / WINO_WGRAD_PLAN below.
+WINOGRAD_CASES = [(2, 64, 64, 13, 30), (2, 64, 64, 20, 20)]
+WINOGRAD_SEAM_CASES = [(3, 64, 64, 20, 20), (1, 64, 64, 10, 9), (2, 64, 64, 13, 30)]  # LIN in both kernels (two); forward LIN, weight gradient in ragged patches
 
 
 def winograd_seams(N, H, W):
@@ -345,3 +349,219 @@ def winograd_seams(N, H, W):
         n, t = g // (th * tw), g % (th * tw)
         pts.append((n, min(2 * (t // tw), H - 1), min(2 * (t % tw), W - 1)))
     return sorted(set(pts))
+
+
+# ---- the Winograd kernels on the paths the training step takes (tests/test_winograd_fp64_gpu.py) ----------------------------------------
+# Every table below is checked against the library's own host-side plan (dbn_winograd_describe, dbn_winograd_rows, dbn_igemm_bn_rows: nothing
+# is launched) in tests/test_winograd_cases_cpu.py: a threshold that moves a case off its path fails there.
+# Weight gradient (csrc/winograd_wgrad_f32.hip).  (N, Ci, Cs, Co, H, W): x has Cs stored channels, Ci of them real.
+# -> (form, groups, nsub, nsplit, reduction): `groups` 8 x 16 patches ('patch') or groups of 32 consecutive tiles ('lin') in the batch, shared
+# among nsplit workgroups per 64 x 64 channel block (nsub blocks); workgroup `split` takes groups split * groups / nsplit up to the next one's first.
+WINO_WGRAD_PLAN = {
+    (5, 128, 128, 128, 40, 40): ('patch', 75, 4, 64, 'serial'),  # uneven 1 - 2 patches per workgroup; 15 patches per image: ranges cross images
+    (3, 256, 256, 256, 29, 77): ('patch', 60, 16, 16, 'serial'),  # 3 - 4 patches per workgroup, ragged in both directions, odd W; 20 patches per image: two ranges cross images
+    (3, 512, 512, 512, 20, 20): ('lin', 12, 64, 4, 'serial'),  # layer4's shape: 3 groups per workgroup, 4 per image: every range but the first crosses images
+    (2, 64, 64, 64, 64, 128): ('patch', 128, 1, 128, 'wide'),  # the wide reduction at its threshold: 4 splits per lane
+    (9, 64, 64, 64, 40, 36): ('patch', 135, 1, 135, 'wide'),  # nsplit % 32 != 0: lanes of 4 and 5 splits
+    (3, 64, 64, 64, 61, 125): ('patch', 192, 1, 192, 'wide'),  # ragged map, 6 splits per lane
+    (2, 128, 128, 64, 61, 125): ('patch', 128, 2, 128, 'wide'),  # two input-channel blocks (nib = 2)
+    (2, 40, 64, 64, 64, 128): ('patch', 128, 1, 128, 'wide'),  # padding channels: the second 32-channel half holds 8 real channels
+    (2, 20, 64, 64, 61, 125): ('patch', 128, 1, 128, 'wide'),  # padding channels: the second half is empty
+    (40, 128, 128, 64, 20, 20): ('lin', 160, 2, 128, 'wide'),  # consecutive-tile form + wide reduction, 1 - 2 groups per workgroup
+}
+WINO_WGRAD_CASES = list(WINO_WGRAD_PLAN)
+# Forward / data gradient (csrc/winograd_f32.hip).  (N, Ci, Cs, Cd, H, W): the kernel's source has Cs stored channels (Ci real), its
+# destination Cd.  The forward conv is Ci -> Cd; the data-gradient launch of the same shape is that of a conv Cd -> Ci (dy: Ci of Cs channels).
+# -> (form, rows): rows = 8 x 16 patches or 32-tile groups in the batch = rows of BatchNorm partials = workgroups per 64 output channels
+WINO_FWD_PLAN = {
+    (2, 64, 64, 64, 15, 77): ('patch', 20),  # ragged in both directions, odd H and W
+    (2, 32, 32, 128, 13, 78): ('patch', 20),  # the same with a second column tile (Cd = 128)
+    (2, 20, 32, 64, 15, 77): ('patch', 20),  # padded source channels
+    (1, 64, 64, 64, 64, 128): ('patch', 64),  # finalize: one full group of 64 rows
+    (1, 64, 64, 64, 65, 113): ('patch', 72),  # finalize: a last group of 8 rows, ragged
+    (1, 64, 64, 64, 71, 241): ('patch', 144),  # finalize: three groups (64, 64, 16), ragged
+    (5, 64, 64, 64, 40, 40): ('lin', 65),  # consecutive-tile form: a last group of one row
+    (17, 64, 64, 64, 20, 20): ('lin', 68),  # consecutive-tile form: a last group of four rows
+}
+WINO_FWD_CASES = list(WINO_FWD_PLAN)
+WINO_PATCH_CASES = [c for c in WINO_FWD_CASES if WINO_FWD_PLAN[c][0] == 'patch']
+WINO_FINAL_CASES = [c for c in WINO_FWD_CASES if WINO_FWD_PLAN[c][1] >= 64]  # the in-kernel finalize with a full first group of 64 rows
+# The implicit-GEMM data gradient with BatchNorm-backward sums and the in-kernel finalize (dbn_igemm_bnsums_t, fp32, tile hint 0):
+# (N, Ci, Co, k, stride, pad, H, W) of the forward conv -> rows of partials (dbn_igemm_bn_rows)
+IGEMM_FINAL_PLAN = {
+    (1, 64, 64, 3, 1, 1, 64, 64): 64,  # one full group
+    (1, 64, 64, 3, 1, 1, 33, 125): 65,  # a last group of one row; the last tile partial
+    (1, 64, 128, 3, 2, 1, 91, 91): 132,  # stride 2, odd map: four parity classes of 34 + 33 + 33 + 32 rows, three groups
+}
+IGEMM_FINAL_CASES = list(IGEMM_FINAL_PLAN)
+
+
+def wino_group_tiles(N, H, W, lin, g):
+    """Group g of a Winograd launch over an [N, H, W] map: (image, [(ty, tx), ...]) — its 2 x 2 tiles in the order of the kernel's k-steps.
+    lin: 32 consecutive tiles of the image's ceil(H / 2) x ceil(W / 2) grid (the last group of an image may hold fewer); patch form: the 4 x 8
+    tiles of an 8 x 16-pixel patch, row by row, INCLUDING those past the map's edge (the kernels multiply zeros there)."""
+    TH, TW = (H + 1) // 2, (W + 1) // 2
+    if lin:
+        n, t = divmod(g, (TH * TW + 31) // 32)
+        return n, [(q // TW, q % TW) for q in range(32 * t, min(32 * t + 32, TH * TW))]
+    pw = (W + 15) // 16
+    n, t = divmod(g, ((H + 7) // 8) * pw)
+    return n, [(4 * (t // pw) + i, 8 * (t % pw) + j) for i in range(4) for j in range(8)]
+
+
+def wino_ranges(groups, nsplit):
+    """The groups g0 .. g1 - 1 of every workgroup of the weight gradient (csrc/winograd_wgrad_f32.hip: g0 = split * groups / nsplit)."""
+    return [(s * groups // nsplit, (s + 1) * groups // nsplit) for s in range(nsplit)]
+
+
+def wino_rows(N, H, W, lin):
+    """(row [N, H, W], pivot [rows, 3]): the row of BatchNorm partials (= workgroup) that holds each pixel in the forward kernel, and the
+    pixel (n, h, w) whose value that workgroup takes as the pivot of its statistics (the first pixel of its first tile)."""
+    TH, TW = (H + 1) // 2, (W + 1) // 2
+    h, w = torch.arange(H).view(H, 1), torch.arange(W).view(1, W)
+    if lin:
+        gpi = (TH * TW + 31) // 32
+        row = ((h // 2) * TW + w // 2) // 32
+        piv = [(n, 2 * (32 * t // TW), 2 * (32 * t % TW)) for n in range(N) for t in range(gpi)]
+    else:
+        pw, gpi = (W + 15) // 16, ((H + 7) // 8) * ((W + 15) // 16)
+        row = (h // 8) * pw + w // 16
+        piv = [(n, 8 * (t // pw), 16 * (t % pw)) for n in range(N) for t in range(gpi)]
+    row = row.expand(H, W).unsqueeze(0) + gpi * torch.arange(N).view(N, 1, 1)
+    return row, torch.tensor(piv)
+
+
+def _border(N, H, W):
+    pts = []
+    for n in range(N):
+        pts += [(n, h, w) for h in (0, H - 1) for w in range(W)] + [(n, h, w) for h in range(H) for w in (0, W - 1)]
+    return pts
+
+
+def _patch_corners(N, H, W):
+    return [(n, h, w) for n in range(N) for i in range(8, H, 8) for j in range(16, W, 16) for h in (i - 1, i) for w in (j - 1, j)]
+
+
+def winograd_wgrad_seams(N, H, W, form, groups, nsplit):
+    """Pixels (n, h, w) on the seams of the Winograd weight gradient's walk, for impulses in dY or in x: the first and the last in-map
+    pixel of every group (patch or 32 consecutive tiles); all four pixels of the first and of the last tile of the first and last group
+    of every workgroup's range g0 .. g1 — and with them the pixel on each side of every image boundary inside a range —; the four pixels
+    around every 8 x 16 patch corner; the whole first and last row and column (x: their halo lies outside the map and must read as zero;
+    ragged maps: the last row and column end inside a patch) — which include the image corners."""
+    lin = form == 'lin'
+    pts = set(_border(N, H, W))
+    if not lin:
+        pts |= set(_patch_corners(N, H, W))
+
+    def ends(g):
+        n, tiles = wino_group_tiles(N, H, W, lin, g)
+        tiles = [t for t in tiles if 2 * t[0] < H and 2 * t[1] < W]
+        return n, tiles[0], tiles[-1]
+
+    for g in range(groups):
+        n, (ty0, tx0), (ty1, tx1) = ends(g)
+        pts |= {(n, 2 * ty0, 2 * tx0), (n, min(2 * ty1 + 1, H - 1), min(2 * tx1 + 1, W - 1))}
+    for g0, g1 in wino_ranges(groups, nsplit):
+        for g in {g0, g1 - 1}:
+            n, first, last = ends(g)
+            pts |= {(n, min(2 * ty + i, H - 1), min(2 * tx + j, W - 1)) for (ty, tx) in (first, last) for i in (0, 1) for j in (0, 1)}
+    return sorted(pts)
+
+
+def winograd_patch_seams(N, H, W):
+    """Pixels on the seams of the forward kernel's patch form: the four pixels around every 8 x 16 patch corner, the whole first and last row and column
+    of every image (the ragged last patch row and column, the image corners) and the first row and column of the ragged patches."""
+    pts = set(_border(N, H, W)) | set(_patch_corners(N, H, W))
+    for n in range(N):
+        pts |= {(n, H // 8 * 8 if H % 8 else H - 8, w) for w in range(0, W, 5)} | {(n, h, W // 16 * 16 if W % 16 else W - 16) for h in range(0, H, 3)}
+    return sorted(pts)
+
+
+def act_coeffs(C, seed):
+    """Dyadic coefficients of the BatchNorm + ReLU applied on load: scale in {1/2, 1, 3/2}, shift a multiple of 1/8 in [-1/2, 1/2]: on x in
+    {-4..4} / 4, fma(x, scale, shift) is a multiple of 1/8 in [-2, 2] — exact in fp32, with or without the fused rounding."""
+    return _ints((C, ), 1, 3, seed) / 2, _ints((C, ), -4, 4, seed + 1) / 8
+
+
+def apply_act(x, scale, shift):
+    """relu(x scale[c] + shift[c]) on an NCHW tensor, in x's precision (float64: exact on the dyadic data)."""
+    return (x * scale.to(x.dtype).view(1, -1, 1, 1) + shift.to(x.dtype).view(1, -1, 1, 1)).clamp_min(0)
+
+
+def winograd_wgrad_emulated(x, dy, form, groups, nsplit, dt):
+    """The Winograd weight gradient as csrc/winograd_wgrad_f32.hip evaluates it, every step before the slab sum in `dt` (float32: every
+    product and addition rounded, elementwise ops only): D = A dY A^T and V = B^T d B per 2 x 2 tile (zero past the map), per workgroup
+    the sum of D (.) V over the tiles of its groups g0 .. g1 — once in the kernel's order and once reversed —, then the sum of the
+    workgroups' slabs in float64 and dg = G^T dU G, cast to float32.  x [N, Ci, H, W], dy [N, Co, H, W] (few channels: the channel pairs
+    are independent of each other).  Returns dict(D, V, slabs, slabs_rev [nsplit, Co, Ci, 4, 4], dg [Co, Ci, 3, 3])."""
+    N, Ci, H, W = x.shape
+    Co = dy.shape[1]
+    lin = form == 'lin'
+    th, tw = ((H + 1) // 2, (W + 1) // 2) if lin else ((H + 7) // 8 * 4, (W + 15) // 16 * 8)
+    xp = torch.zeros((N, Ci, 2 * th + 2, 2 * tw + 2), dtype=dt)
+    xp[:, :, 1:H + 1, 1:W + 1] = x.to(dt)
+    yp = torch.zeros((N, Co, 2 * th, 2 * tw), dtype=dt)
+    yp[:, :, :H, :W] = dy.to(dt)
+    d = torch.stack([torch.stack([xp[:, :, i:i + 2 * th:2, j:j + 2 * tw:2] for j in range(4)], -1) for i in range(4)], -2)  # [N, Ci, th, tw, 4, 4]
+    y2 = torch.stack([torch.stack([yp[:, :, i::2, j::2] for j in range(2)], -1) for i in range(2)], -2)  # [N, Co, th, tw, 2, 2]
+    bt, g, at = BT.to(dt), G.to(dt), AT.to(dt)
+    mm = _mm32 if dt == torch.float32 else torch.matmul
+    V = mm(mm(bt.expand(N, Ci, th, tw, 4, 4), d), bt.t().expand(N, Ci, th, tw, 4, 4))
+    D = mm(mm(at.t().expand(N, Co, th, tw, 4, 2), y2), at.expand(N, Co, th, tw, 2, 4))
+    slabs = torch.zeros((2, nsplit, Co, Ci, 4, 4), dtype=dt)
+    for s, (g0, g1) in enumerate(wino_ranges(groups, nsplit)):
+        order = [(n, t) for gq in range(g0, g1) for n, tiles in [wino_group_tiles(N, H, W, lin, gq)] for t in tiles]
+        for k, seq in enumerate((order, order[::-1])):
+            for n, (ty, tx) in seq:
+                slabs[k, s] = slabs[k, s] + D[n, :, ty, tx][:, None] * V[n, :, ty, tx][None]
+    dU = slabs[0].double().sum(0)
+    dg = torch.matmul(torch.matmul(G.double().t().expand(Co, Ci, 3, 4), dU), G.double().expand(Co, Ci, 4, 3))
+    return dict(D=D, V=V, slabs=slabs[0], slabs_rev=slabs[1], dg=dg.float())
+
+
+def fold_slabs(slab, scale=1.0):
+    """Phase 2 of the Winograd weight gradient on the host: slab [nsplit, nob, nib, 4, 4, 64, 64] (any float type) -> float64 sum over the
+    splits, G^T . G per (o, i), times scale, cast to float32: [nob 64, nib 64, 3, 3]."""
+    nsplit, nob, nib = slab.shape[:3]
+    dU = slab.double().sum(0).permute(0, 4, 1, 5, 2, 3).reshape(nob * 64, nib * 64, 4, 4)
+    dg = torch.matmul(torch.matmul(G.double().t(), dU), G.double())
+    return (dg * scale).float()
+
+
+def wino_wgrad_data(case, kind):
+    """(x [N, Ci, H, W], dy [N, Co, H, W]) in float64 of a WINO_WGRAD_CASES case.  'dense': both on {-4..4} / 4; 'sparse dy' / 'sparse x':
+    that operand zero except for impulses (1, -2, 1 / 2, in the last channel and in others) on winograd_wgrad_seams, the other dense."""
+    N, Ci, Cs, Co, H, W = case
+    form, groups, _, nsplit, _ = WINO_WGRAD_PLAN[case]
+    x, dy = dense_x((N, Ci, H, W), 31), dense_x((N, Co, H, W), 34)
+    if kind == 'sparse dy':
+        (dy, ) = impulse_maps(N, Co, H, W, winograd_wgrad_seams(N, H, W, form, groups, nsplit), 0)
+    elif kind == 'sparse x':
+        (x, ) = impulse_maps(N, Ci, H, W, winograd_wgrad_seams(N, H, W, form, groups, nsplit), 0)
+    else:
+        assert kind == 'dense', kind
+    return x, dy
+
+
+def wino_sums_data(case, accumulate):
+    """Dyadic operands of a Winograd data gradient with BatchNorm-backward sums, small enough that the two sums per channel are exact in
+    fp32 in any order (tests/test_winograd_cases_cpu.py bounds sum |g| and sum |g xhat| on their grids): dy in {-1, 0, 1} / 4, w in
+    {-2..2} / 2, the accumulate base in {-8..8} / 8 — dx on the 2^-3 grid —; y, y2 in {-2..2} / 2, rstd in {1, 2}, mean in {-1/2, 0, 1/2} —
+    xhat = fma(y, rstd, -mean rstd) on the 2^-1 grid, |xhat| <= 3 —; the mask fma(y, msc, msh) with msc in {-1, -1/2, 1/2, 1}, msh an odd
+    multiple of 1/8 (never zero, half of the channels positive: there a pixel read as 0 outside the map would count), or z in {-1, 1}."""
+    N, Ci, Cs, Cd, H, W = case
+    pm = lambda shape, seed: _ints(shape, 0, 1, seed) * 2 - 1
+    d = dict(dy=_ints((N, Ci, H, W), -1, 1, 41) / 4, w=dense_w((Ci, Cd, 3, 3), 42, winograd=True),
+             base=_ints((N, Cd, H, W), -8, 8, 43) / 8 if accumulate else None,
+             y=_ints((N, Cd, H, W), -2, 2, 44) / 2, y2=_ints((N, Cd, H, W), -2, 2, 45) / 2, z=pm((N, Cd, H, W), 46),
+             mean=_ints((Cd, ), -1, 1, 47) / 2, rstd=_ints((Cd, ), 1, 2, 48), mean2=_ints((Cd, ), -1, 1, 49) / 2, rstd2=_ints((Cd, ), 1, 2, 50),
+             msc=pm((Cd, ), 51) * _ints((Cd, ), 1, 2, 52) / 2, msh=pm((Cd, ), 53) * (2 * _ints((Cd, ), 0, 3, 54) + 1) / 8)
+    d['dx'] = conv2d_dgrad(d['dy'], d['w'], 1, 1, H, W) + (d['base'] if accumulate else 0)
+    return d
+
+
+def bn_backward_sums(dx, y, mean, rstd, m):
+    """float64: g = dx [m > 0]; (sum g, sum g xhat, sum |g|, sum |g xhat|) per channel with xhat = (y - mean) rstd."""
+    g = dx.double() * (m > 0)
+    t = g * (y.double() - mean.double().view(1, -1, 1, 1)) * rstd.double().view(1, -1, 1, 1)
+    return g.sum((0, 2, 3)), t.sum((0, 2, 3)), g.abs().sum((0, 2, 3)), t.abs().sum((0, 2, 3))

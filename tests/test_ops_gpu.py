@@ -1949,8 +1949,10 @@ def test_winograd_conv3x3(N, Ci, Cs, Co, H, W, with_bn):
     """dbn_winograd_conv_bn_f32: 3x3 / stride 1 / pad 1 forward convolution through Winograd F(2x2, 3x3) in fp32 (the BasicBlock, FPN
     smooth and head convs of resnet.py:70-91, segmentation_body.py:55-61, segmentation_head.py:24-25) against F.conv2d in fp64, with
     the bias and — with_bn — the folded train-mode BatchNorm statistics (scale / shift / saved mean / rstd / running statistics)
-    against F.batch_norm.  Small maps (40 x 40: layer3, 20 x 20: layer4, odd sizes) run in the consecutive-tile form, wide maps whose
-    size is not a multiple of the 8 x 16 patch with masked ragged patches.  fp32 arithmetic with another summation order than the direct form: tolerance 2e-6 of the output scale
+    against F.batch_norm.  Every map up to 72 pixels wide runs in the consecutive-tile (LIN) form: all shapes here but 8 x 96, which runs
+    the patch form on six WHOLE 8 x 16 patches per image.  The patch form's masked ragged patches, its statistics over them, Cd > 64 and
+    apply-on-load in it are pinned in tests/test_winograd_fp64_gpu.py (conv_ref.WINO_FWD_PLAN names the form of every case there).
+    fp32 arithmetic with another summation order than the direct form: tolerance 2e-6 of the output scale
     per element (the direct kernels' own fp32 rounding is ~3e-7 at K = 2304).  Cs > Ci: the source tensor carries padding channels."""
     x = rnd(N, Ci, H, W, seed=1)
     w = rnd(Co, Ci, 3, 3, seed=2, scale=(2.0 / (Ci * 9))**0.5)
@@ -2006,7 +2008,9 @@ def test_winograd_dgrad_with_bn_sums(N, Ci, Co, H, W, mask, accumulate):
     the rotated / transposed filter panel, [+ accumulate], and in its epilogue the two sums of the BatchNorm backward that consumes dx
     (mask recomputed from the BatchNorm's own output, or a mask tensor with a SECOND BatchNorm over the same gradient) plus the
     in-kernel finalize — against autograd in fp64 (conv -> BN -> ReLU chain of resnet.py:70-91; same contract as
-    test_batchnorm_backward_sums_in_the_data_gradient for the implicit-GEMM kernels)."""
+    test_batchnorm_backward_sums_in_the_data_gradient for the implicit-GEMM kernels).  All seven maps are at most 40 pixels wide: the kernel
+    runs its consecutive-tile (LIN) form throughout, with 1 - 13 partial rows, so the finalize folds ONE row group.  The patch form on
+    ragged maps and the finalize over two and three row groups are pinned in tests/test_winograd_fp64_gpu.py."""
     import ctypes
     x = rnd(N, Ci, H, W, seed=1).requires_grad_(True)
     w = rnd(Co, Ci, 3, 3, seed=2, scale=(2.0 / (Ci * 9))**0.5)
@@ -2089,7 +2093,11 @@ def test_winograd_weight_gradient(N, Ci, Cs, Co, H, W):
     (torch.autograd's conv weight gradient of resnet.py:70-91, segmentation_body.py:55-61, segmentation_head.py:24-25) against
     autograd in fp64: ragged maps (zero-filled patch edges), odd sizes, padding channels (Cs > Ci), several channel blocks, scale.
     Tolerance 4e-6 of the gradient's scale per element (the direct kernel's own fp32 rounding is ~1e-6 here); bit-reproducible
-    from run to run; against the direct kernel to fp32 rounding."""
+    from run to run; against the direct kernel to fp32 rounding.  The weight gradient's own rule chooses the form (not the forward
+    kernel's): the patch form on 16 x 32, 8 x 16, 24 x 40, 40 x 40, 13 x 30, 64 x 64, 13 x 13 and 40 x 36, the consecutive-tile (LIN) form
+    on 20 x 20, 9 x 29, 25 x 25 and 10 x 9.  In every shape the split count equals the group count (at most 64): each workgroup multiplies
+    ONE patch or 32-tile group and the serial slab reduction runs.  Several groups per workgroup, ranges across images and the wide
+    reduction (nsplit >= 128) are pinned in tests/test_winograd_fp64_gpu.py."""
     x = rnd(N, Ci, H, W, seed=1)
     w = rnd(Co, Ci, 3, 3, seed=2).double().requires_grad_(True)
     y = F.conv2d(x.double(), w, None, 1, 1)
