@@ -12,6 +12,7 @@ from .augment import DeviceBatches, augment_images, image_collate, plan_augment,
 from .photometric import (adjust_brightness, adjust_contrast, adjust_hue, adjust_saturation, color_jitter_images,  # noqa: F401
                           plan_color_jitter)
 from .degrade import blur_weights, degrade_images, degrade_records, gaussian_blur, gaussian_noise, plan_degrade  # noqa: F401
+from .synth import SynthTextBatches, plan_synth_text, render_synth_text, synth_records  # noqa: F401
 from .word_crops import (crop_words, perspective_maps, polygon_ribbons, polygon_ribbons_device, rectify_from_ribbons,  # noqa: F401
                          rectify_words)
 from .render import draw_outlines, image_views, minmax_scale_u8, overlay_heatmap, render_detections  # noqa: F401

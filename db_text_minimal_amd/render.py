@@ -284,7 +284,8 @@ def glyph_table():
     `descender`, `cap_height`, `first` (code point of glyph 0), `advance` (int64 [G]), `contours` (per glyph a list of
     int64 [P, 2] closed polylines in font units), and what the kernel takes: `edges` (int32 [E, 4] of ax, ay, bx, by;
     every contour closed, horizontal edges left out: the winding rule never counts them) and `index` (int32 [G, 6] of
-    first edge, edges, xmin, ymin, xmax, ymax)"""
+    first edge, edges, xmin, ymin, xmax, ymax); `edges_all` and `index_all` are the same with EVERY edge of the closed
+    contours, for a glyph under a rotation, where an edge that is horizontal in font units counts (synth.py)"""
     if _font:
         return _font
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'fonts', 'dejavu_sans.txt')
@@ -310,18 +311,24 @@ def glyph_table():
             want -= 1
     if len(adv) != _LAST - _FIRST + 1 or want or len(head) != 4:
         raise ValueError('%s is not the table of code points %d .. %d' % (path, _FIRST, _LAST))
-    edges, index = [], np.zeros((len(adv), _GLYPH), np.int32)
+    edges, index, every = [], np.zeros((len(adv), _GLYPH), np.int32), []
     for g, cs in enumerate(contours):
         first = sum(len(e) for e in edges)
         for c in cs:
             e = np.concatenate([c, np.roll(c, -1, 0)], 1)
             edges.append(e[e[:, 1] != e[:, 3]])
+            every.append(e)
         if cs:
             p = np.concatenate(cs)
             index[g] = first, sum(len(e) for e in edges) - first, p[:, 0].min(), p[:, 1].min(), p[:, 0].max(), p[:, 1].max()
     if index[:, 1].max() > _GLYPH_EDGES:
         raise ValueError('%s: a glyph of more than %d edges' % (path, _GLYPH_EDGES))
-    _font.update(head, first=_FIRST, advance=np.array(adv, np.int64), contours=contours, edges=np.concatenate(edges).astype(np.int32), index=index)
+    index_all = index.copy()
+    index_all[:, 1] = [sum(len(c) for c in cs) for cs in contours]
+    index_all[:, 0] = np.cumsum(index_all[:, 1]) - index_all[:, 1]
+    index_all[index_all[:, 1] == 0, 0] = 0
+    _font.update(head, first=_FIRST, advance=np.array(adv, np.int64), contours=contours, edges=np.concatenate(edges).astype(np.int32), index=index,
+                 edges_all=np.concatenate(every).astype(np.int32), index_all=index_all)
     return _font
 
 

@@ -1131,6 +1131,33 @@ int dbn_color_jitter_host(const unsigned char* in, unsigned char* out, long byte
 int dbn_degrade_u8(const unsigned char* in, unsigned char* out, long bytes, const long long* hdesc, const long long* desc, int N, const int* htiles,
                    const int* tiles, long T, const short* normal, void* stream);
 
+/* ---- Synthetic scene text (csrc/synth.hip; db_text_minimal_amd/synth.py): a background and over it glyph instances under any affine map,
+ * anti-aliased by 16 samples per pixel, in exact integers, written as packed uint8 [H][W][3] RGB images (the definition: DESIGN.md section
+ * 41; THIS PROJECT'S DEFINITION, PARITY UNPINNED against SynthText or any renderer).  One launch, one workgroup per tile of 32 x 32 pixels.
+ * desc int64 [N][8] per image = {byte offset of its first pixel (any alignment; ascending, images do not overlap), H, W, first tile over the
+ * batch, base colour r | g << 8 | b << 16, amplitudes A_0 | A_1 << 8 | A_2 << 16 (0 .. 64 each; octave o has cells of 64 >> 2 o pixels), the
+ * 64-bit seed of the noise, 0}.  backgrounds: NULL (the procedural background of desc) or a packed batch of the same layout, read instead;
+ * `out` must not overlap it.
+ * recs int64 [R][9] per glyph instance = {image, glyph, a00, a01, a10, a11, tx, ty, colour r | g << 8 | b << 16}: font vertex v sits at (a00 vx +
+ * a01 vy, a10 vx + a11 vy) + t on the lattice of 2^20 units per pixel (font y points up: an upright glyph has a11 < 0).  Sample (i, j), i, j =
+ * 0 .. 3, of pixel (px, py) sits at (2^20 px + (2 i + 1) 2^17, 2^20 py + (2 j + 1) 2^17); it is inside when the winding sum of
+ * dbn_draw_glyphs' rule about the transformed edges is not 0; cov = the samples inside; per channel cur = (cov fg + (16 - cov) cur + 8) >> 4,
+ * instance after instance in ascending record order.  An instance is evaluated only if |a| < 2^19, |t| <= 2^35, its glyph has 1 .. 512 edges
+ * and the transformed glyph box spans less than 2^30 per axis (then every cross product is below 2^62); any other is skipped.
+ * edges int32 [E][4] = {ax, ay, bx, by} in font units, EVERY edge of the closed contours (one that is horizontal after the transform never
+ * counts); glyphs int32 [G][6] = {first edge, edges, xmin, ymin, xmax, ymax}, the box holding every edge of the glyph, |.| <= 2^14.
+ * bins int32 [B]: T rows {image, y0, x0, end} of the tiles, per image in row-major order, images in order, every tile once; then the lists:
+ * tile k lists bins[end of tile k - 1 (4 T for k = 0) .. end of tile k), record indices of its image in strictly ascending order; the last
+ * end is B.  A tile lists (at least) the evaluated instances whose box meets it.
+ * Descriptors, records, bins and glyphs are taken twice: in host memory (hdesc, hrecs, hbins, hglyphs), checked before anything is
+ * launched (descriptors against `bytes`, the tile list, glyph ranges against E, image and glyph indices and colours of the records, bins
+ * in range, ascending and of their tile's image), and in device memory, which the kernel reads; an instance whose device record disagrees
+ * with its tile's image, G or E is skipped.  1 <= N <= 65535, 1 <= H, W <= 16384; R may be 0 (hrecs, recs NULL): the background alone.
+ * Every byte of every image is stored exactly once; bytes of `out` that belong to no image are not written.  No atomics, no float arithmetic. */
+int dbn_synth_text_u8(const unsigned char* backgrounds, unsigned char* out, long bytes, const long long* hdesc, const long long* desc, int N,
+                      const long long* hrecs, const long long* recs, long R, const int* hbins, const int* bins, long T, long B, const int* edges,
+                      long E, const int* hglyphs, const int* glyphs, int G, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
