@@ -18,6 +18,7 @@ from .word_crops import (crop_words, perspective_maps, polygon_ribbons, polygon_
 from .render import draw_outlines, image_views, minmax_scale_u8, overlay_heatmap, render_detections  # noqa: F401
 from .render import draw_dots, draw_labels, draw_scores, draw_words, text_size  # noqa: F401
 from .recognise import AttnLabelConverter, CTCLabelConverter, greedy_decode, recognize_words, words_to_input  # noqa: F401
+from .spotting import Lexicon, TextClasses, TextSpottingEvaluator, edit_distances  # noqa: F401
 from .jpeg import (CorruptJpeg, JpegCoefficients, JpegEncodeError, JpegError, JpegStreams, UnsupportedJpeg, decode_coefficients, decode_jpeg,  # noqa: F401
                    decode_jpeg_batch, encode_jpeg, encode_jpeg_batch, entropy_decode, entropy_encode, entropy_encode_device, forward_coefficients, jpeg_collate,
                    jpeg_info, jpeg_multiscan_collate, optimal_huffman_table, quant_tables, save_jpegs, entropy_decode_device, jpeg_stream_collate, parse_streams)

@@ -24,6 +24,7 @@ _INT_MAX = 2 ** 31 - 1
 _AT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # DBN_AT_* of include/dbnet_hip.h
 BLANK, EOS = 0, 1  # '[blank]' of the CTC table, '[s]' of the attention table
 _MODES = {'ctc': 0, 'attn': 1}
+_LEXICON_STEPS = 64  # decode steps recognize_words(lexicon=) takes: the pattern of dbn_lexicon_nearest is one 64-bit word
 
 
 def input_table():
@@ -121,12 +122,13 @@ def greedy_decode(logits, mode='ctc', lengths=None):
     return codes, count, score
 
 
-def _fetch(codes, count, score=None):
-    """codes [B, T], count [B] (and score [B]) on the host from ONE device-to-host copy"""
-    parts = [codes, count[:, None]] + ([score.view(torch.int32)[:, None]] if score is not None else [])
+def _fetch(codes, count, score=None, more=()):
+    """codes [B, T], count [B] (and score [B], and further int32 [B] columns `more`) on the host from ONE device-to-host copy"""
+    parts = [codes, count[:, None]] + ([score.view(torch.int32)[:, None]] if score is not None else []) + [m[:, None] for m in more]
     host = torch.cat(parts, 1).cpu().numpy()
     T = codes.shape[1]
-    return host[:, :T], host[:, T], (host[:, T + 1].copy().view(np.float32) if score is not None else None)
+    got = host[:, :T], host[:, T], (host[:, T + 1].copy().view(np.float32) if score is not None else None)
+    return got + tuple(host[:, host.shape[1] - len(more) + j] for j in range(len(more))) if more else got
 
 
 class _LabelConverter:
@@ -177,7 +179,7 @@ def _box_rows(boxes):
 
 
 def recognize_words(images, boxes, model, converter, prediction='CTC', batch_size=512, batch_max_length=25, rgb=False, size=SIZE,
-                    scores=None, min_score=None, polygons=None, segments=32, ends='auto', ribbons='host'):
+                    scores=None, min_score=None, polygons=None, segments=32, ends='auto', ribbons='host', lexicon=None, max_distance=None):
     """From images and detected boxes to strings: crop_words -> words_to_input -> model -> greedy_decode -> converter.decode.
 
     images, boxes, size, scores, min_score: as crop_words takes them.  Or polygons= (with boxes = None) instead of boxes:
@@ -187,7 +189,15 @@ def recognize_words(images, boxes, model, converter, prediction='CTC', batch_siz
     prediction 'CTC', model(image, text_for_pred, is_train=False) for 'Attn'; it returns logits [b, T, C].
     Returns, per image, a list of {'box': the box row (int16 [4, 2]), 'pred': str, 'score': float} in box order ('box': the
     polygon as given, [P, 2], for polygons=); for ready crops one flat list with 'box': None.  One device-to-host copy for
-    all words."""
+    all words.
+    lexicon: a spotting.Lexicon built over the classes of this converter.  Every dict gains 'word', the lexicon's nearest entry
+    by edit distance (the smallest index among equals), or None when there is none within max_distance (None: any distance)
+    or the group is empty, and 'distance' (-1 for an empty group); 'pred' and 'score' are as without it.  A lexicon of more than
+    one group is searched per image: the group of a word is its image index.  The search runs on the device codes (one more
+    entry point, dbn_lexicon_nearest) before the copy back, which then carries index and distance with the codes.  It takes
+    recognisers of at most 64 decode steps (logits [b, T <= 64, C]: the query is the one-word pattern of the kernel); a
+    longer one raises ValueError before the model runs where the steps are known then ('Attn': batch_max_length + 1), else
+    at the model's first chunk."""
     if boxes is not None and polygons is not None:
         raise ValueError('boxes or polygons, not both')
     if not (isinstance(ribbons, str) and ribbons in ('host', 'device')):
@@ -201,6 +211,10 @@ def recognize_words(images, boxes, model, converter, prediction='CTC', batch_siz
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError('batch_size must be positive')
+    if lexicon is not None and lexicon.n_groups != 1 and boxes is None and polygons is None:
+        raise ValueError('a lexicon of %d groups needs images: ready crops have no image index' % lexicon.n_groups)
+    if lexicon is not None and mode == 'attn' and batch_max_length + 1 > _LEXICON_STEPS:
+        raise ValueError('lexicon=: an attention recogniser of %d steps; at most %d' % (batch_max_length + 1, _LEXICON_STEPS))
     if polygons is not None:
         polygons = list(polygons)
         crops, index = rectify_words(images, polygons, size, scores, min_score, segments, ends, ribbons=ribbons)
@@ -220,16 +234,29 @@ def recognize_words(images, boxes, model, converter, prediction='CTC', batch_siz
             image = x[k0:k0 + batch_size]
             text_for_pred = torch.zeros((image.shape[0], batch_max_length + 1), dtype=torch.long, device=x.device)
             logits = model(image, text_for_pred) if mode == 'ctc' else model(image, text_for_pred, is_train=False)
+            if lexicon is not None and logits.shape[1] > _LEXICON_STEPS:  # (known only from the model's output: at its first chunk)
+                raise ValueError('lexicon=: the recogniser gives %d steps; at most %d' % (logits.shape[1], _LEXICON_STEPS))
             outs.append(greedy_decode(logits, mode))
     words = []
     if outs:
         T = max(c.shape[1] for c, _, _ in outs)
         pad = [torch.nn.functional.pad(c, (0, T - c.shape[1]), value=-1) for c, _, _ in outs]
-        codes, count, score = _fetch(torch.cat(pad), torch.cat([n for _, n, _ in outs]), torch.cat([s for _, _, s in outs]))
+        d_codes, d_count, d_score = torch.cat(pad), torch.cat([n for _, n, _ in outs]), torch.cat([s for _, _, s in outs])
+        if lexicon is None:
+            codes, count, score = _fetch(d_codes, d_count, d_score)
+        else:
+            group = index[:, 0].astype(np.int32) if lexicon.n_groups != 1 else None
+            near = lexicon.nearest(d_codes, d_count, group, head=converter)
+            codes, count, score, near_index, near_dist = _fetch(d_codes, d_count, d_score, near)
+            found = lexicon.words_of(near_index, near_dist, np.zeros(len(near_index), np.int64) if group is None else group, max_distance)
         words = list(zip(converter.decode_host(codes, count), score.tolist()))
+    made = [{'pred': p, 'score': s} for p, s in words]
+    if lexicon is not None:
+        for w, (word, distance) in zip(made, found if outs else []):
+            w['word'], w['distance'] = word, distance
     if index is None:
-        return [{'box': None, 'pred': p, 'score': s} for p, s in words]
+        return [dict(box=None, **w) for w in made]
     result = [[] for _ in range(n_images)]
-    for (n, k), (p, s) in zip(index.tolist(), words):
-        result[n].append({'box': rows[n][k], 'pred': p, 'score': s})
+    for (n, k), w in zip(index.tolist(), made):
+        result[n].append(dict(box=rows[n][k], **w))
     return result

@@ -614,6 +614,30 @@ long dbn_greedy_decode_ws_bytes(int B, int T);
 int dbn_greedy_decode(int at, const void* logits, int B, int T, int C, const int* lengths, int mode, void* ws, int* codes, int* count,
                       float* score, void* stream);
 
+/* ---- edit distances between strings of classes: text scoring and lexicon correction (csrc/lexicon.hip,
+ *      db_text_minimal_amd/spotting.py).  A string is a run of bytes, one class 0 .. 254 each; class 255
+ *      matches nothing, not even itself.  Distance: unit-cost Levenshtein (insert, delete, substitute), exact. ---- */
+/* P independent pairs, one launch, one wave per pair.  Pair p: the pattern is row p of pattern [P][T] (1 <= T <= 64), its
+ * first pat_len[p] classes (clamped to 0 .. T); the text is the text_len[p] bytes (text_len NULL: text_off[p + 1] -
+ * text_off[p]) from byte text_off[p] of text, of any length.  text holds n_text bytes, and no byte outside it is read
+ * whatever the two tables hold (offset and length are clamped).  dist [P]: every element written. */
+int dbn_edit_distance_pairs(const unsigned char* pattern, int T, const int* pat_len, const unsigned char* text, long n_text, const int* text_off,
+                            const int* text_len, int P, int* dist, void* stream);
+/* bytes of workspace dbn_lexicon_nearest needs (8 per query) */
+long dbn_lexicon_ws_bytes(int K);
+/* K queries against a lexicon on the device, three launches, no host synchronisation.  Query k: row k of query [K][T]
+ * (1 <= T <= 64), its first qlen[k] classes (clamped to 0 .. T), searched in group group[k] (group NULL: group 0).
+ * The lexicon: NB blocks of 64 entry slots, ordered by (group, length); group g owns the blocks grp_blk[g] ..
+ * grp_blk[g + 1] - 1 (grp_blk [G + 1]; max_blocks = the largest such count).  Block b holds a multiple of four positions
+ * of 64 bytes each from byte blk_off[b] of data, position-major: byte blk_off[b] + pos * 64 + lane is class pos of slot
+ * b * 64 + lane; ent_len [NB * 64] is the slot's length (at most the block's positions; -1: a padding slot) and ent_idx
+ * [NB * 64] its index in the caller's order.  index [K], dist [K]: the entry of the group with the smallest distance and,
+ * among equals, the smallest ent_idx, and that distance; (-1, -1) where the group is empty or outside 0 .. G - 1.  Every
+ * element written; two runs agree in every bit.  ws: dbn_lexicon_ws_bytes(K) bytes, 8-byte aligned, any contents. */
+int dbn_lexicon_nearest(const unsigned char* query, int T, const int* qlen, const int* group, int K, const unsigned char* data, const int* blk_off,
+                        const int* ent_len, const int* ent_idx, const int* grp_blk, int G, int NB, int max_blocks, void* ws, int* index, int* dist,
+                        void* stream);
+
 /* ---- text boxes from probability maps: boxes_from_bitmap of postprocess.py:105-141 (csrc/detect.hip,
  *      db_text_minimal_amd/postprocess.py detect_boxes).  PARITY UNPINNED against cv2 / pyclipper. ---- */
 /* One record per candidate (72 bytes):
